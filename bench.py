@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark (BASELINE.json): integrated states/sec of adaptive Dopri5 steps.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+
+`--dump-outputs DIR` writes the timed solver's state after the K timed attempts as DIR/<name>.npy, so that two builds can be compared
+output for output (see dump_outputs).  It serves the solver workloads (c2, c4-shard, c4-n1); the side workloads refuse it.
 
 N > 1 without a launcher (no WORLD_SIZE in the environment): this process starts the N ranks itself (a child
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py <same flags>`), relays rank 0's
@@ -12,7 +15,8 @@ runs each stage (rendezvous, transport probe, communicator, negotiation, timed r
 
 Set-up (untimed, like the framework's GEMM tuning) ends with XDE_BENCH_SETTLE_MS (default 100) milliseconds of attempts — their number is
 `solver.settle_steps` on the line — so that a short timed block reads what the same block reads when repeated (profiles/r05_settle.txt);
-then W warm-up steps, then EXACTLY K timed attempts; the same K-step block is repeated twice more (`ms_per_step_blocks`).
+then W warm-up steps, then EXACTLY K timed attempts.  `--repeat-blocks R` times R more K-step blocks after them on the same solver
+(`ms_per_step_blocks`: the spread of a short timed region on the box); `value` / `ms_per_step` always come from the first block.
 
 A "step" is ONE attempted Dopri5 step over the whole batch: 6 stage combines (xde_stage_combine), 6 calls
 of the user's func (a framework call: torch matmul ``y @ A^T``), one fused error-norm launch and the device
@@ -230,6 +234,31 @@ def time_unsharded(B, D, dtype, pipeline, device, steps, warmup):
             "settle_steps": settle, "global_batch": B, "dim": D, "n_gpus": 1}
 
 
+DUMP_SETTLE_MORE = 320  # --dump-outputs: settle attempts after the first 32 (~100 ms at the headline size), fixed so that the number of
+# attempts before the dump, and so the trajectory, is the same on every run
+DUMP_MAX_BYTES = int(os.environ.get("XDE_BENCH_DUMP_MAX_BYTES", 64 * 10 ** 6))  # all dumped files together
+
+
+def dump_outputs(out_dir, solver):
+    """--dump-outputs: the solver's state after the timed attempts (what a caller stepping this solver gets back) as .npy files: y (the
+    state), f (its derivative, the next attempt's first stage), both in the state dtype, with rows.npy the row indices they hold, and
+    t.npy = [t0, t1, dt] (float64).  When y and f would pass DUMP_MAX_BYTES together, both are cut to ONE fixed, seeded sample of rows
+    (the same rows on every run, listed in rows.npy)."""
+    torch.cuda.synchronize()
+    st = solver.rk_state
+    y, f = (x.detach().reshape(x.shape[0], -1) for x in (st.y1, st.f1))
+    n = y.shape[0]
+    row_bytes = (y.shape[1] + f.shape[1]) * y.element_size() + 8  # (+ its index in rows.npy)
+    keep = min(n, max(1, (DUMP_MAX_BYTES - 4096) // row_bytes))  # (4096: t.npy and the four file headers)
+    rows = torch.arange(n) if keep == n else torch.randperm(n, generator=torch.Generator().manual_seed(0))[:keep].sort().values
+    os.makedirs(out_dir, exist_ok=True)
+    idx = rows.to(y.device)
+    np.save(os.path.join(out_dir, "y.npy"), y[idx].cpu().numpy())
+    np.save(os.path.join(out_dir, "f.npy"), f[idx].cpu().numpy())
+    np.save(os.path.join(out_dir, "rows.npy"), rows.numpy().astype(np.float64))
+    np.save(os.path.join(out_dir, "t.npy"), np.asarray([float(st.t0), float(st.t1), float(st.dt)], dtype=np.float64))
+
+
 def pmc_traffic(B, D, dtype):
     """HBM bytes per launch of the stage-combine kernel from the committed rocprofv3 counter passes (`--pmc FETCH_SIZE` and
     `--pmc WRITE_SIZE`, separate runs, reduced by profiles/tools/pmc_summarise.py) -> (bytes or None, where it comes from).
@@ -294,8 +323,8 @@ def p2p_probe_child():
 
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     local = 0 if os.environ.get("XDE_BENCH_REHEARSAL", "0") == "1" else int(os.environ.get("LOCAL_RANK", "0"))
-    if os.environ.get("XDE_BENCH_TEST_PROBE_FAIL") == str(rank):  # test hook: this rank's probe dies the hard way, before anything else
-        os.abort()
+    if os.environ.get("XDE_BENCH_TEST_PROBE_FAIL") == str(rank):  # test hook: this rank's probe dies before anything else, without a word
+        os._exit(70)
     wd = Watchdog(rank)
     wd.stage("probe: rendezvous", 45)
     dist.init_process_group("gloo")
@@ -339,7 +368,10 @@ def p2p_probe_child():
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200, help="timed attempted steps (200 x 0.34 ms = 68 ms at the headline size)")
+    ap.add_argument("--steps", type=int, default=200, help="timed attempted steps: exactly this many (200 x 0.31 ms = 63 ms at the headline "
+                    "size).  Set-up, warm-up and the extra measurements (cpu baseline, whole odeint() calls, func share) are not timed steps")
+    ap.add_argument("--repeat-blocks", type=int, default=0, help="after the timed steps, time this many more blocks of --steps attempts "
+                    "on the same solver (ms_per_step_blocks: the spread of a short timed region); they do not enter value / ms_per_step")
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--batch", type=int, default=None, help="rows PER GPU (default: 65536 at N=1 = config 2; 524288/N at N>1 = config 4)")
     ap.add_argument("--dim", type=int, default=None, help="default: 128 at N=1 (config 2), 64 at N>1 (config 4)")
@@ -371,6 +403,12 @@ def parse_args():
     ap.add_argument("--no-tunable-op", action="store_true",
                     help="leave PyTorch's TunableOp off (by default the framework tunes the GEMMs inside the user's func during "
                          "warm-up: same fp32 arithmetic, a better hipBLASLt/rocBLAS kernel for the shape)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the solver holds after the --steps timed attempts (before any --repeat-blocks) — the state y and "
+                         "its derivative f (state dtype), rows.npy (the row indices they hold: one fixed seeded sample of rows when the "
+                         "whole would pass 64 MB in all) and t.npy = [t0, t1, dt] (float64) — as DIR/<name>.npy (rank 0's shard at N > 1).  "
+                         "The settle phase then takes a fixed number of attempts instead of a fixed time, so the same arguments give the "
+                         "same trajectory on every run.  Solver workloads only (c2, c4-shard, c4-n1)")
     ap.add_argument("--event-period", type=int, default=11,
                     help="time every p-th launch of each kernel inside the timed region (a dispatch-stamped launch costs the step ~5 us: "
                          "every 5th one made the step 2.5 %% longer, every 11th ~1 %%; 11 is coprime with the 6 combines per step, so all "
@@ -460,6 +498,8 @@ def main():
     args = parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.repeat_blocks < 0:
+        raise SystemExit("--steps must be >= 1 and --repeat-blocks >= 0")
     if args.probe_p2p:
         raise SystemExit(p2p_probe_child())
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -484,6 +524,8 @@ def main():
         args.workload = "c2"
     if args.workload != "c2":
         args.tunable_op = enable_tunable_op(args.tunable_op)  # (single-process workloads: no probe to wait for)
+    if args.dump_outputs is not None and args.workload != "c2":
+        raise SystemExit("--dump-outputs is implemented for the headline solver workloads (c2, c4-shard, c4-n1) only")
     if args.workload != "c2":  # the side workloads live in bench_side.py
         import types
 
@@ -554,9 +596,10 @@ def main():
             dist.barrier()
             torch.cuda.synchronize()
 
-    def timed_run(kind, ex, steps, warmup, events, pipeline=None, blocks=1):
+    def timed_run(kind, ex, steps, warmup, events, pipeline=None, blocks=1, dump=None):
         """Build a solver on transport `kind`, let it settle, warm up, and time EXACTLY `steps` attempted steps between barriers:
-        every rank's own clock stops after its stream has drained, the job's time is the MAX over the ranks."""
+        every rank's own clock stops after its stream has drained, the job's time is the MAX over the ranks.  `dump`: a directory the
+        solver's state goes to right after those steps (rank 0), before the `blocks - 1` repeats."""
         if os.environ.get("XDE_BENCH_TEST_HANG") == str(rank):  # test hook: this rank never joins the set-up's first collective
             time.sleep(10 ** 6)
         with torch.no_grad():
@@ -588,7 +631,7 @@ def main():
             solver.advance(32)
             torch.cuda.synchronize()
             per_step = (time.perf_counter() - t_s) / 32
-            more = min(4096, max(0, int(SETTLE_MS * 1e-3 / max(per_step, 1e-6)) - 32))
+            more = min(4096, max(0, int(SETTLE_MS * 1e-3 / max(per_step, 1e-6)) - 32)) if args.dump_outputs is None else DUMP_SETTLE_MORE
             if dist is not None:  # (every rank takes the same number of attempts: the norm exchange is collective)
                 box = torch.tensor([more], dtype=torch.int64)
                 dist.all_reduce(box, op=dist.ReduceOp.MAX)
@@ -616,8 +659,10 @@ def main():
             return cb, el
 
         c, elapsed = block()  # THE timed region: `value` / `ms_per_step` come from this block alone
-        # ... and the same block twice more, back to back on the same solver: the line then says how far a 20-step block moves from
-        # one run to the next on this box (`ms_per_step_blocks`), which one shot cannot
+        if dump is not None and rank == 0:
+            dump_outputs(dump, solver)
+        # ... and, if asked (--repeat-blocks), the same block again, back to back on the same solver: the line then says how far a
+        # 20-step block moves from one run to the next on this box (`ms_per_step_blocks`), which one shot cannot
         repeats = [elapsed]
         for _ in range(blocks - 1):
             _c, el = block()  # (`c`, the counters the line reports, stay those of the timed region)
@@ -630,7 +675,8 @@ def main():
         return solver, c, elapsed, prof, settle
 
     wd.stage("set-up + warm-up + timed region", 600)
-    solver, c, elapsed, prof, settle = timed_run(exchange_kind, exchange, args.steps, args.warmup, not args.no_kernel_events, blocks=3)
+    solver, c, elapsed, prof, settle = timed_run(exchange_kind, exchange, args.steps, args.warmup, not args.no_kernel_events,
+                                                 blocks=1 + args.repeat_blocks, dump=args.dump_outputs)
     block_ms = [1e3 * el / args.steps for el in timed_run.blocks]
     # func's own share of a step, measured apart (the same GEMM, back to back, on torch's stream — where func runs)
     with torch.no_grad():
@@ -657,8 +703,8 @@ def main():
         "steps": args.steps,
         "warmup": args.warmup,
         "ms_per_step": ms_per_step,
-        # the same `steps`-step block three times back to back (the first is the one `value` is computed from): the spread of a short
-        # timed region on THIS box, in the line itself
+        # the `steps`-step block, then each --repeat-blocks repeat back to back (the first is the one `value` is computed from): the
+        # spread of a short timed region on THIS box, in the line itself
         "ms_per_step_blocks": block_ms,
         "higher_is_better": True,
         "scaling": scaling,

@@ -22,7 +22,7 @@ def _run(*extra):
 
 
 def test_bench_json_contract():
-    j = _run("--pipeline", "lag")  # (per-kernel HIP events need eager launches; "auto" replays a hipGraph at this small size)
+    j = _run("--pipeline", "lag", "--repeat-blocks", "2")  # (per-kernel HIP events need eager launches; "auto" replays a hipGraph at this small size)
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
                 "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert key in j, key
@@ -157,7 +157,7 @@ def test_bench_two_rank_rehearsal_takes_the_settle_phase_too():
 
 def test_bench_survives_a_peer_to_peer_probe_that_crashes():
     """The peer-to-peer transport makes its first contact with a machine in CHILD processes.  XDE_BENCH_TEST_PROBE_FAIL=1 makes rank 1's
-    probe abort() (what a GPU fault inside the probe would look like to its parent): its peers' probes then run out of partners, every
+    probe exit at once with a non-zero status (what a probe that dies would look like to its parent): its peers' probes then run out of partners, every
     rank hears that the probe failed, the job moves on to the next transport together (rehearsal: the host-staged all-reduce) and the line
     says what happened."""
     # (XDE_BENCH_STAGE_SCALE: the surviving probe waits for its partner until its rendezvous stage — 45 s — runs out; half of that here)
@@ -184,3 +184,47 @@ def test_bench_extra_measurement_that_hangs_keeps_the_headline_and_exits_nonzero
     j = json.loads(lines[0])
     assert j["watchdog_expired"] == "whole odeint() calls" and j["value"] > 0 and j["n_gpus"] == 1 and "odeint_ms_T2" not in j
     assert "stage 'whole odeint() calls' has run for" in r.stderr
+
+
+def test_bench_dump_outputs_are_the_solved_state(tmp_path):
+    """--dump-outputs writes the solver's state after exactly settle + W + K attempts: y agrees with the exact solution
+    y0 exp(A^T t1) of the linear ODE at the dumped t1 (to the solver's global error: ~3e-4 of max|y| here, bar 2e-3, while y has moved
+    ~1.4 max|y| from y0), and f = y A^T.  A second run with the same arguments and a 1 MB budget dumps one seeded sample of rows
+    (rows.npy) for both arrays: the same attempts, the same values at those rows."""
+    import numpy as np
+    import torch
+
+    def run(d, budget=None):
+        env = dict(os.environ, **({"XDE_BENCH_DUMP_MAX_BYTES": str(budget)} if budget else {}))
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "3", "--batch", "4096",
+                            "--no-cpu-baseline", "--no-odeint", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, cwd=ROOT,
+                           env=env)
+        assert r.returncode == 0, r.stderr[-3000:]
+        j = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+        assert j["solver"]["n_steps"] == j["solver"]["settle_steps"] + 3 + 7 and "ms_per_step_blocks" in j and len(j["ms_per_step_blocks"]) == 1
+        assert sum(f.stat().st_size for f in d.iterdir()) <= (budget or 64 * 10 ** 6)
+        return j, {n: np.load(d / (n + ".npy")) for n in ("y", "f", "rows", "t")}
+
+    j1, a = run(tmp_path / "whole")
+    assert a["y"].shape == a["f"].shape == (4096, 128) and a["y"].dtype == a["f"].dtype == np.float32
+    assert a["rows"].dtype == np.float64 and np.array_equal(a["rows"], np.arange(4096)) and a["t"].dtype == np.float64
+    g = torch.Generator().manual_seed(1)
+    U = 0.1 * torch.randn(128, 128, generator=g, dtype=torch.float32)
+    AT = (U - U.T).T.double()
+    y0 = torch.randn(4096, 128, generator=torch.Generator().manual_seed(0)).double()
+    t1 = float(a["t"][1])
+    assert t1 > 1.0 and a["t"][0] < t1 and a["t"][2] > 0
+    exact = (y0 @ torch.linalg.matrix_exp(AT * t1)).numpy()
+    scale = float(np.abs(exact).max())
+    assert float(np.abs(a["y"] - exact).max()) <= 2e-3 * scale
+    assert float(np.abs(a["y"] - y0.numpy()).max()) > 0.5 * scale  # (a dump of y0 fails the line above by far)
+    f_ref = a["y"].astype(np.float64) @ AT.numpy()
+    assert float(np.abs(a["f"] - f_ref).max()) <= 1e-5 * float(np.abs(f_ref).max())
+
+    j2, b = run(tmp_path / "sampled", budget=10 ** 6)
+    rows = b["rows"].astype(np.int64)
+    assert 0 < len(rows) < 4096 and np.array_equal(rows, np.unique(rows)) and np.array_equal(b["rows"], rows)
+    assert b["y"].shape == b["f"].shape == (len(rows), 128)
+    assert j2["solver"]["n_steps"] == j1["solver"]["n_steps"] and np.allclose(b["t"], a["t"], rtol=1e-6, atol=0)
+    for n in ("y", "f"):
+        assert np.allclose(b[n], a[n][rows], rtol=1e-5, atol=1e-6 * float(np.abs(a[n]).max())), n

@@ -187,6 +187,13 @@ def test_sharded_adjoint_equals_unsharded(tmp_path, cpu_double, norm, t_grad, wo
     looks at every parameter adjoint, which is a sum over ALL rows) and under "seminorm": every rank takes the unsharded run's
     backward step sequence, solution rows and d/dy0 rows equal the unsharded run's, and EVERY rank ends with the parameter (and
     time) gradients of the global loss."""
+    if world > 5 and torch.cuda.is_available():
+        # backward() starts the autograd engine, which asks every device type for its device count: with a GPU visible, each rank
+        # process then initialises the HIP runtime, which opens /dev/kfd and the card's render node, and a card admits at most 6
+        # processes (this one included).  Hiding the device does not prevent that: with HIP_VISIBLE_DEVICES empty or -1 the device
+        # count is 0 but both files are open all the same, and CUDA_VISIBLE_DEVICES / ROCR_VISIBLE_DEVICES empty change neither.  The
+        # CPU double needs no GPU: these cases run wherever none is visible, and the world-2 and world-3 cases run either way.
+        pytest.skip("{} rank processes would each open the visible GPU (autograd engine start-up)".format(world))
     port = _free_port()
     mp.spawn(_adjoint_worker, args=(world, port, str(tmp_path), norm, t_grad), nprocs=world, join=True)
     rs = [np.load(tmp_path / "adj{}.npz".format(r)) for r in range(world)]
