@@ -79,6 +79,14 @@ SYMBOLS = (
     "xde_prof_collect",
 )
 
+# the entry points of include/xde_hip_backprop.h (back-propagation through the accepted steps of an adaptive solve): bound only
+# when the library exports them; odeint(..., options={"backprop": "steps"}) refuses to start without them
+BACKPROP_SYMBOLS = (
+    "xde_stage_cotangent",
+    "xde_dense_cotangent",
+)
+XDE_BP_MAX_X = XDE_MAX_K + 2
+
 
 class XdeCtrl(C.Structure):
     """xde_ctrl_t"""
@@ -291,6 +299,11 @@ def load_library():
         lib.xde_prof_enable.argtypes = [i32]
         lib.xde_prof_collect.restype = i32
         lib.xde_prof_collect.argtypes = [C.POINTER(C.c_int64), dp, dp]
+        if all(hasattr(lib, sym) for sym in BACKPROP_SYMBOLS):
+            lib.xde_stage_cotangent.restype = i32
+            lib.xde_stage_cotangent.argtypes = [vp, vp, vpp, dp, dp, i32, i64, i32, vp]
+            lib.xde_dense_cotangent.restype = i32
+            lib.xde_dense_cotangent.argtypes = [vpp, vp, dp, i32, C.c_uint32, i64, i32, vp]
         if lib.xde_abi_version() != ABI_VERSION:
             raise XdeError("libxde_hip.so ABI version mismatch")
         if lib.xde_sizeof_ctrl() != C.sizeof(XdeCtrl):
@@ -751,6 +764,29 @@ class HipBackend:
         rc = self.lib.xde_scale_fanout(_ptr_array(outs), g.data_ptr(), _dbl_array(factors), len(outs), _ptr(dt_dev), g.numel(),
                                        dtype_code(g.dtype), self._stream(g))
         self._check(rc, "xde_scale_fanout")
+
+    # -- back-propagation through the accepted steps (include/xde_hip_backprop.h) ------------------------------------------
+    def backprop_supported(self):
+        return all(hasattr(self.lib, sym) for sym in BACKPROP_SYMBOLS)
+
+    def stage_cotangent(self, out, xs, coef, *, out2=None, coef2=None):
+        """out = sum_j xs[j] * coef[j]  [, out2 = sum_j xs[j] * coef2[j]]: one launch, every operand read once."""
+        self._require_device(out, out2, *xs)
+        rc = self.lib.xde_stage_cotangent(out.data_ptr(), _ptr(out2), _ptr_array(xs), _dbl_array(coef),
+                                          _dbl_array(coef2) if coef2 is not None else None, len(xs), out.numel(),
+                                          dtype_code(out.dtype), self._stream(out))
+        self._check(rc, "xde_stage_cotangent")
+
+    def dense_cotangent(self, outs, g_rows, weights, acc_mask=0):
+        """outs = [y0, y1, y_mid, f0, f1] cotangents (None: not written) <- the [G, n] rows ``g_rows`` times the G x 5 ``weights``;
+        bit k of ``acc_mask``: outs[k] accumulates."""
+        self._require_device(g_rows, *[o for o in outs if o is not None])
+        G = len(weights)
+        n = g_rows.numel() // G if G else 0
+        flat = [float(w) for row in weights for w in row]
+        rc = self.lib.xde_dense_cotangent((C.c_void_p * 5)(*[_ptr(o) for o in outs]), g_rows.data_ptr(), _dbl_array(flat), G,
+                                          int(acc_mask) & 0x1F, n, dtype_code(g_rows.dtype), self._stream(g_rows))
+        self._check(rc, "xde_dense_cotangent")
 
     def hermite_gather(self, val, der, his, his_t, lags):
         """his [..., T, D] (contiguous), his_t [T], lags [L]  ->  val, der [..., L, D]."""

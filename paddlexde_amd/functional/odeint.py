@@ -44,7 +44,22 @@ def odeint(
             return tuple(importer(v) for v in sol) if isinstance(sol, tuple) else importer(sol)
     if not torch.is_tensor(t_span):
         t_span = torch.as_tensor(t_span)
-    if _wants_autograd(func, y0, t_span, solver):
+    if isinstance(options, dict) and "backprop" in options:
+        options = dict(options)
+        mode = options.pop("backprop")
+        route = _backprop_route(mode, func, y0, t_span, solver, options)
+        if route == "adjoint":
+            from .odeint_adjoint import odeint_adjoint
+
+            params = None if isinstance(func, torch.nn.Module) else ()
+            return odeint_adjoint(func, y0, t_span, rtol=rtol, atol=atol, solver=solver, options=options, adjoint_params=params)
+        if route == "steps":
+            from ..solver._rk_backprop import odeint_steps
+
+            options.pop("pipeline", None)
+            return odeint_steps(func, y0, t_span, solver, rtol=rtol, atol=atol, options=options, params=_trainable(func))
+        # a fixed solver records its own graph; an adaptive "steps" solve with nothing to differentiate is a plain solve
+    elif _wants_autograd(func, y0, t_span, solver):
         # The reference's adaptive solvers are eager framework ops, so `odeint(..., solver=Dopri5)` + `loss.backward()`
         # trains there.  Here the adaptive step kernels read dt from device memory and record no autograd graph; rather than
         # hand back a silently detached result, the call is served by the adjoint method (gradients w.r.t. y0, func's
@@ -65,6 +80,37 @@ def odeint(
     solution = xde.format(solution)
 
     return solution
+
+
+def _trainable(func):
+    return [p for p in func.parameters() if p.requires_grad] if isinstance(func, torch.nn.Module) else []
+
+
+def _backprop_route(mode, func, y0, t_span, solver, options):
+    """``options["backprop"]``: how an adaptive solve is trained.  "adjoint": the continuous adjoint (odeint_adjoint), the route a
+    call without the key takes too, minus its warning.  "steps": back-propagation through the accepted steps, the gradient of the
+    reference's discrete map with the step sizes held constant (solver/_rk_backprop.py).  Returns "adjoint", "steps" or None (a
+    plain solve: a fixed solver, which back-propagates through its steps anyway, or nothing to differentiate)."""
+    if mode not in ("steps", "adjoint"):
+        raise ValueError("options['backprop'] must be 'steps' or 'adjoint', got {!r}".format(mode))
+    fixed = isinstance(solver, type) and issubclass(solver, FixedSolver)
+    if fixed:
+        if mode == "adjoint":
+            raise ValueError("options['backprop'] = 'adjoint' applies to adaptive solvers: fixed solvers back-propagate through "
+                             "their steps; call odeint_adjoint for the continuous adjoint of a fixed-step solve")
+        return None
+    if mode == "adjoint":
+        return "adjoint" if _wants_autograd(func, y0, t_span, solver) else None
+    if isinstance(y0, (tuple, list)):
+        raise NotImplementedError("options['backprop'] = 'steps' takes a tensor y0, not a tuple")
+    if options.get("process_group") is not None:
+        raise NotImplementedError("options['backprop'] = 'steps' does not run sharded solves (process_group)")
+    if options.get("pipeline", "sync") != "sync":
+        raise ValueError("options['backprop'] = 'steps' runs on the 'sync' pipeline (got pipeline={!r})".format(options["pipeline"]))
+    if torch.is_grad_enabled() and t_span.requires_grad:
+        raise NotImplementedError("options['backprop'] = 'steps' gives no gradient with respect to t_span; "
+                                  "odeint_adjoint does")
+    return "steps" if _wants_autograd(func, y0, t_span, solver) else None
 
 
 _ROUTE_WARNED = False
