@@ -18,6 +18,7 @@ ABI_VERSION = 6
 XDE_F32, XDE_F64 = 0, 1
 XDE_MAX_K, XDE_MAX_SEG, XDE_MAX_STAGE = 14, 16, 13
 XDE_MAX_PACK = 64
+XDE_BP_MAX_X = XDE_MAX_K + 2  # operands of one xde_stage_cotangent launch
 XDE_P2P_MAX_RANKS, XDE_P2P_HANDLE_BYTES = 16, 64
 COMBINE_RK, COMBINE_FUSE, COMBINE_WFUSE = 0, 1, 2
 NORM_RMS, NORM_LINF = 0, 1
@@ -26,66 +27,6 @@ STATUS_OK, STATUS_DT_UNDERFLOW, STATUS_NONFINITE, STATUS_MAX_STEPS = 0, 1, 2, 3
 KID_NAMES = ("combine", "errnorm", "control", "dense", "scalednorm", "finalize", "commit", "combine_fuse", "combine_wfuse")
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libxde_hip.so")
-
-# every symbol include/xde_hip.h declares (tests/test_cabi.py checks the export list against the header)
-SYMBOLS = (
-    "xde_last_error",
-    "xde_abi_version",
-    "xde_sizeof_ctrl",
-    "xde_sizeof_ctrl_params",
-    "xde_sizeof_segments",
-    "xde_workspace_bytes",
-    "xde_stage_combine",
-    "xde_stage_combine_pre",
-    "xde_stage_combine_pre_weighted",
-    "xde_error_norm_partial",
-    "xde_error_norm_control",
-    "xde_error_ratio",
-    "xde_scaled_norm_partial",
-    "xde_norm_finalize",
-    "xde_norm_result",
-    "xde_rk_control",
-    "xde_ctrl_init",
-    "xde_ctrl_retarget",
-    "xde_initial_step",
-    "xde_initial_step_fused",
-    "xde_scaled_norm2_partial",
-    "xde_initial_step_tail",
-    "xde_ctrl_read",
-    "xde_host_alloc",
-    "xde_host_free",
-    "xde_ctrl_wait",
-    "xde_dense_eval",
-    "xde_commit",
-    "xde_pack_segments",
-    "xde_dense_commit",
-    "xde_hermite_gather",
-    "xde_history_gather",
-    "xde_lag_grad_workspace_bytes",
-    "xde_lag_grad",
-    "xde_scale_fanout",
-    "xde_graph_replace_memsets",
-    "xde_p2p_mailbox_bytes",
-    "xde_p2p_alloc",
-    "xde_p2p_free",
-    "xde_p2p_export",
-    "xde_p2p_import",
-    "xde_p2p_close",
-    "xde_p2p_exchange",
-    "xde_p2p_error",
-    "xde_p2p_error_info",
-    "xde_p2p_rk_control",
-    "xde_prof_enable",
-    "xde_prof_collect",
-)
-
-# the entry points of include/xde_hip_backprop.h (back-propagation through the accepted steps of an adaptive solve): bound only
-# when the library exports them; odeint(..., options={"backprop": "steps"}) refuses to start without them
-BACKPROP_SYMBOLS = (
-    "xde_stage_cotangent",
-    "xde_dense_cotangent",
-)
-XDE_BP_MAX_X = XDE_MAX_K + 2
 
 
 class XdeCtrl(C.Structure):
@@ -176,6 +117,71 @@ class XdeError(RuntimeError):
     pass
 
 
+_vp, _dp, _i32, _i64, _dbl = C.c_void_p, C.POINTER(C.c_double), C.c_int, C.c_int64, C.c_double
+_vpp, _params, _segs = C.POINTER(C.c_void_p), C.POINTER(XdeCtrlParams), C.POINTER(XdeSegments)
+
+# symbol -> (restype, argtypes) of every entry point include/xde_hip.h declares (tests/test_cabi.py checks the export list against the
+# header); argtypes None: not declared (the zero-argument queries)
+PROTOTYPES = {
+    "xde_last_error": (C.c_char_p, []),
+    "xde_abi_version": (_i32, None),
+    "xde_sizeof_ctrl": (_i64, None),
+    "xde_sizeof_ctrl_params": (_i64, None),
+    "xde_sizeof_segments": (_i64, None),
+    "xde_workspace_bytes": (_i64, None),
+    "xde_stage_combine": (_i32, [_vp, _vp, _vp, _vpp, _vp, _dp, _i32, _i32, _dbl, _dbl, _vp, _i64, _i32, _vp, _dp, _dbl, C.c_uint32, _vp]),
+    "xde_stage_combine_pre": (_i32, [_vp, _vp, _vp, _vp, _vpp, _dp, _i32, _dbl, _vp, _i64, _i32, C.c_uint32, _vp]),
+    "xde_stage_combine_pre_weighted": (_i32, [_vp, _vp, _vp, _vpp, _dp, _i32, _dbl, _dbl, _vp, _i64, _i32, _dbl, _vp]),
+    "xde_error_norm_partial": (_i32, [_vpp, _vp, _dp, _i32, _vp, _vp, _vp, _dbl, _dbl, _dbl, _vp, _segs, _i32, _i32, _vp, _vp, _vp]),
+    "xde_error_norm_control": (_i32, [_vpp, _vp, _dp, _i32, _vp, _vp, _vp, _segs, _i32, _vp, _vp, _vp, _params, _vp, _vp, _vp, _vp, _vp]),
+    "xde_error_ratio": (_i32, [_vp, _vpp, _vp, _dp, _i32, _vp, _vp, _vp, _dbl, _dbl, _dbl, _vp, _i64, _i32, _vp, _vp]),
+    "xde_scaled_norm_partial": (_i32, [_vp, _vp, _vp, _dbl, _dbl, _segs, _i32, _i32, _vp, _i32, _vp]),
+    "xde_norm_finalize": (_i32, [_vp, _i32, _vp, _vp]),
+    "xde_norm_result": (_i32, [_vp, _dp, _i32, _i32, _i32, _vp, _vp]),
+    "xde_rk_control": (_i32, [_vp, _params, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "xde_ctrl_init": (_i32, [_vp, _params, _dbl, _dbl, C.c_int32, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "xde_ctrl_retarget": (_i32, [_vp, _params, _vp, C.c_int32, _vp, _vp]),
+    "xde_initial_step": (_i32, [_i32, _vp, _vp, _params, _dbl, _vp, _i32, _vp, _vp]),
+    "xde_initial_step_fused": (_i32, [_i32, _vp, _vp, _vp, _segs, _i32, _vp, _params, _dbl, _vp, _i32, _vp, C.c_int32, _vp, _vp, _vp, _i64,
+                                      _vp]),
+    "xde_scaled_norm2_partial": (_i32, [_vp, _vp, _dbl, _dbl, _segs, _i32, _i32, _vp, _vp]),
+    "xde_initial_step_tail": (_i32, [_i32, _vp, _vp, _params, _dbl, _vp, _i32, _vp, C.c_int32, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "xde_ctrl_read": (_i32, [_vp, C.POINTER(XdeCtrl), _vp]),
+    "xde_host_alloc": (_i32, [_i64, C.POINTER(C.c_void_p)]),
+    "xde_host_free": (_i32, [_vp]),
+    "xde_ctrl_wait": (_i32, [_vp, _i64, _dbl, C.POINTER(XdeCtrl)]),
+    "xde_dense_eval": (_i32, [_vp, _vpp, _vp, _dp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i64, _vp]),
+    "xde_commit": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp]),
+    "xde_pack_segments": (_i32, [_vp, _vpp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _dp, _i32, _i64, _i32, _vp]),
+    "xde_dense_commit": (_i32, [_vp, _vpp, _dp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp]),
+    "xde_hermite_gather": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
+    "xde_history_gather": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "xde_lag_grad_workspace_bytes": (_i64, [_i32]),
+    "xde_lag_grad": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
+    "xde_scale_fanout": (_i32, [_vpp, _vp, _dp, _i32, _vp, _i64, _i32, _vp]),
+    "xde_graph_replace_memsets": (_i32, [_vp, C.POINTER(C.c_int)]),
+    "xde_p2p_mailbox_bytes": (_i64, None),
+    "xde_p2p_alloc": (_i32, [C.POINTER(C.c_void_p)]),
+    "xde_p2p_free": (_i32, [_vp]),
+    "xde_p2p_export": (_i32, [_vp, _vp]),
+    "xde_p2p_import": (_i32, [_vp, C.POINTER(C.c_void_p)]),
+    "xde_p2p_close": (_i32, [_vp]),
+    "xde_p2p_exchange": (_i32, [_vp, _vp, _vpp, _i32, _i32, _i32, _i64, _vp]),
+    "xde_p2p_error": (_i32, [_vp, C.POINTER(C.c_int64), _vp]),
+    "xde_p2p_error_info": (_i32, [_vp, C.POINTER(C.c_int64), _i32, _vp]),
+    "xde_p2p_rk_control": (_i32, [_vp, _params, _vp, _vp, _vpp, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "xde_prof_enable": (_i32, [_i32]),
+    "xde_prof_collect": (_i32, [C.POINTER(C.c_int64), _dp, _dp]),
+}
+# the entry points of include/xde_hip_backprop.h (back-propagation through the accepted steps of an adaptive solve)
+BACKPROP_PROTOTYPES = {
+    "xde_stage_cotangent": (_i32, [_vp, _vp, _vpp, _dp, _dp, _i32, _i64, _i32, _vp]),
+    "xde_dense_cotangent": (_i32, [_vpp, _vp, _dp, _i32, C.c_uint32, _i64, _i32, _vp]),
+}
+SYMBOLS = tuple(PROTOTYPES)
+BACKPROP_SYMBOLS = tuple(BACKPROP_PROTOTYPES)
+
+
 class _Work:
     """The small per-solve device buffers of an adaptive solver."""
 
@@ -187,12 +193,50 @@ class _Work:
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 
 
+def stream_of(device):
+    """Raw hipStream_t of torch's current stream on the ROCm ``device`` (a key of the per-stream caches)."""
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    return _raw_stream(idx) if _raw_stream is not None else torch.cuda.current_stream(device).cuda_stream
+
+
 _lib = None
 _lib_lock = threading.Lock()
 
 
+_REBUILD = "rebuild it with `python -m paddlexde_amd.csrc.build --force`"
+
+
+def _declare(lib, sym):
+    proto = PROTOTYPES.get(sym) or BACKPROP_PROTOTYPES[sym]
+    try:
+        fn = getattr(lib, sym)
+    except AttributeError:
+        raise XdeError("libxde_hip.so does not export {}: it is stale or not this project's build; {}".format(sym, _REBUILD)) from None
+    fn.restype = proto[0]
+    if proto[1] is not None:
+        fn.argtypes = proto[1]
+    return fn
+
+
+def _bind(lib):
+    """Declare every prototype on ``lib``: first that it is the ABI this binding speaks, then the struct layouts, then the rest."""
+    _declare(lib, "xde_last_error")
+    version = _declare(lib, "xde_abi_version")()
+    if version != ABI_VERSION:
+        raise XdeError("libxde_hip.so ABI version mismatch: the library is version {}, this binding is version {}; {}".format(
+            version, ABI_VERSION, _REBUILD))
+    if _declare(lib, "xde_sizeof_ctrl")() != C.sizeof(XdeCtrl):
+        raise XdeError("xde_ctrl_t layout mismatch between header and ctypes mirror")
+    if _declare(lib, "xde_sizeof_ctrl_params")() != C.sizeof(XdeCtrlParams):
+        raise XdeError("xde_ctrl_params_t layout mismatch between header and ctypes mirror")
+    if _declare(lib, "xde_sizeof_segments")() != C.sizeof(XdeSegments):
+        raise XdeError("xde_segments_t layout mismatch between header and ctypes mirror")
+    for sym in SYMBOLS + BACKPROP_SYMBOLS:
+        _declare(lib, sym)
+
+
 def load_library():
-    """dlopen libxde_hip.so and declare prototypes.  Raises if it has not been built."""
+    """dlopen libxde_hip.so and declare prototypes.  Raises if it has not been built, or is not the library this binding speaks to."""
     global _lib
     if _lib is not None:
         return _lib
@@ -205,113 +249,7 @@ def load_library():
                 "or `python -m paddlexde_amd.csrc.build`. There is no CPU fallback.".format(LIB_PATH)
             )
         lib = C.CDLL(LIB_PATH)
-        vp, dp, i32, i64, dbl = C.c_void_p, C.POINTER(C.c_double), C.c_int, C.c_int64, C.c_double
-        vpp = C.POINTER(C.c_void_p)
-        lib.xde_last_error.restype = C.c_char_p
-        lib.xde_last_error.argtypes = []
-        lib.xde_abi_version.restype = i32
-        lib.xde_sizeof_ctrl.restype = i64
-        lib.xde_sizeof_ctrl_params.restype = i64
-        lib.xde_sizeof_segments.restype = i64
-        lib.xde_workspace_bytes.restype = i64
-        lib.xde_stage_combine.restype = i32
-        lib.xde_stage_combine.argtypes = [vp, vp, vp, vpp, vp, dp, i32, i32, dbl, dbl, vp, i64, i32, vp, dp, dbl, C.c_uint32, vp]
-        lib.xde_stage_combine_pre.restype = i32
-        lib.xde_stage_combine_pre.argtypes = [vp, vp, vp, vp, vpp, dp, i32, dbl, vp, i64, i32, C.c_uint32, vp]
-        lib.xde_stage_combine_pre_weighted.restype = i32
-        lib.xde_stage_combine_pre_weighted.argtypes = [vp, vp, vp, vpp, dp, i32, dbl, dbl, vp, i64, i32, dbl, vp]
-        lib.xde_error_norm_partial.restype = i32
-        lib.xde_error_norm_partial.argtypes = [vpp, vp, dp, i32, vp, vp, vp, dbl, dbl, dbl, vp, C.POINTER(XdeSegments), i32, i32, vp, vp, vp]
-        lib.xde_error_norm_control.restype = i32
-        lib.xde_error_norm_control.argtypes = [vpp, vp, dp, i32, vp, vp, vp, C.POINTER(XdeSegments), i32, vp, vp, vp,
-                                               C.POINTER(XdeCtrlParams), vp, vp, vp, vp, vp]
-        lib.xde_error_ratio.restype = i32
-        lib.xde_error_ratio.argtypes = [vp, vpp, vp, dp, i32, vp, vp, vp, dbl, dbl, dbl, vp, i64, i32, vp, vp]
-        lib.xde_scaled_norm_partial.restype = i32
-        lib.xde_scaled_norm_partial.argtypes = [vp, vp, vp, dbl, dbl, C.POINTER(XdeSegments), i32, i32, vp, i32, vp]
-        lib.xde_norm_finalize.restype = i32
-        lib.xde_norm_finalize.argtypes = [vp, i32, vp, vp]
-        lib.xde_norm_result.restype = i32
-        lib.xde_norm_result.argtypes = [vp, dp, i32, i32, i32, vp, vp]
-        lib.xde_rk_control.restype = i32
-        lib.xde_rk_control.argtypes = [vp, C.POINTER(XdeCtrlParams), vp, vp, vp, vp, vp, vp, vp]
-        lib.xde_ctrl_init.restype = i32
-        lib.xde_ctrl_init.argtypes = [vp, C.POINTER(XdeCtrlParams), dbl, dbl, C.c_int32, vp, vp, vp, i64, vp, vp]
-        lib.xde_ctrl_retarget.restype = i32
-        lib.xde_ctrl_retarget.argtypes = [vp, C.POINTER(XdeCtrlParams), vp, C.c_int32, vp, vp]
-        lib.xde_initial_step.restype = i32
-        lib.xde_initial_step.argtypes = [i32, vp, vp, C.POINTER(XdeCtrlParams), dbl, vp, i32, vp, vp]
-        lib.xde_initial_step_fused.restype = i32
-        lib.xde_initial_step_fused.argtypes = [i32, vp, vp, vp, C.POINTER(XdeSegments), i32, vp, C.POINTER(XdeCtrlParams), dbl, vp, i32, vp,
-                                               C.c_int32, vp, vp, vp, i64, vp]
-        lib.xde_scaled_norm2_partial.restype = i32
-        lib.xde_scaled_norm2_partial.argtypes = [vp, vp, dbl, dbl, C.POINTER(XdeSegments), i32, i32, vp, vp]
-        lib.xde_initial_step_tail.restype = i32
-        lib.xde_initial_step_tail.argtypes = [i32, vp, vp, C.POINTER(XdeCtrlParams), dbl, vp, i32, vp, C.c_int32, vp, vp, vp, i64, vp, vp]
-        lib.xde_host_alloc.restype = i32
-        lib.xde_host_alloc.argtypes = [i64, C.POINTER(C.c_void_p)]
-        lib.xde_host_free.restype = i32
-        lib.xde_host_free.argtypes = [vp]
-        lib.xde_ctrl_wait.restype = i32
-        lib.xde_ctrl_wait.argtypes = [vp, i64, dbl, C.POINTER(XdeCtrl)]
-        lib.xde_ctrl_read.restype = i32
-        lib.xde_ctrl_read.argtypes = [vp, C.POINTER(XdeCtrl), vp]
-        lib.xde_dense_eval.restype = i32
-        lib.xde_dense_eval.argtypes = [vp, vpp, vp, dp, i32, vp, vp, vp, vp, vp, vp, i32, i64, i32, i64, vp]
-        lib.xde_scale_fanout.restype = i32
-        lib.xde_scale_fanout.argtypes = [vpp, vp, dp, i32, vp, i64, i32, vp]
-        lib.xde_hermite_gather.restype = i32
-        lib.xde_hermite_gather.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp]
-        lib.xde_history_gather.restype = i32
-        lib.xde_history_gather.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, vp]
-        lib.xde_lag_grad_workspace_bytes.restype = i64
-        lib.xde_lag_grad_workspace_bytes.argtypes = [i32]
-        lib.xde_lag_grad.restype = i32
-        lib.xde_lag_grad.argtypes = [vp, vp, vp, i64, i32, i32, i32, vp, vp]
-        lib.xde_dense_commit.restype = i32
-        lib.xde_dense_commit.argtypes = [vp, vpp, dp, i32, vp, vp, vp, vp, vp, vp, i32, i64, i32, vp]
-        lib.xde_commit.restype = i32
-        lib.xde_commit.argtypes = [vp, vp, vp, vp, vp, i64, i32, vp]
-        lib.xde_graph_replace_memsets.restype = i32
-        lib.xde_graph_replace_memsets.argtypes = [vp, C.POINTER(C.c_int)]
-        lib.xde_p2p_mailbox_bytes.restype = i64
-        lib.xde_p2p_alloc.restype = i32
-        lib.xde_p2p_alloc.argtypes = [C.POINTER(C.c_void_p)]
-        lib.xde_p2p_free.restype = i32
-        lib.xde_p2p_free.argtypes = [vp]
-        lib.xde_p2p_export.restype = i32
-        lib.xde_p2p_export.argtypes = [vp, vp]
-        lib.xde_p2p_import.restype = i32
-        lib.xde_p2p_import.argtypes = [vp, C.POINTER(C.c_void_p)]
-        lib.xde_p2p_close.restype = i32
-        lib.xde_p2p_close.argtypes = [vp]
-        lib.xde_p2p_exchange.restype = i32
-        lib.xde_p2p_exchange.argtypes = [vp, vp, vpp, i32, i32, i32, i64, vp]
-        lib.xde_pack_segments.restype = i32
-        lib.xde_pack_segments.argtypes = [vp, vpp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), dp, i32, i64, i32, vp]
-        lib.xde_p2p_error.restype = i32
-        lib.xde_p2p_error.argtypes = [vp, C.POINTER(C.c_int64), vp]
-        lib.xde_p2p_error_info.restype = i32
-        lib.xde_p2p_error_info.argtypes = [vp, C.POINTER(C.c_int64), i32, vp]
-        lib.xde_p2p_rk_control.restype = i32
-        lib.xde_p2p_rk_control.argtypes = [vp, C.POINTER(XdeCtrlParams), vp, vp, vpp, i32, i32, i64, vp, vp, vp, vp, vp]
-        lib.xde_prof_enable.restype = i32
-        lib.xde_prof_enable.argtypes = [i32]
-        lib.xde_prof_collect.restype = i32
-        lib.xde_prof_collect.argtypes = [C.POINTER(C.c_int64), dp, dp]
-        if all(hasattr(lib, sym) for sym in BACKPROP_SYMBOLS):
-            lib.xde_stage_cotangent.restype = i32
-            lib.xde_stage_cotangent.argtypes = [vp, vp, vpp, dp, dp, i32, i64, i32, vp]
-            lib.xde_dense_cotangent.restype = i32
-            lib.xde_dense_cotangent.argtypes = [vpp, vp, dp, i32, C.c_uint32, i64, i32, vp]
-        if lib.xde_abi_version() != ABI_VERSION:
-            raise XdeError("libxde_hip.so ABI version mismatch")
-        if lib.xde_sizeof_ctrl() != C.sizeof(XdeCtrl):
-            raise XdeError("xde_ctrl_t layout mismatch between header and ctypes mirror")
-        if lib.xde_sizeof_ctrl_params() != C.sizeof(XdeCtrlParams):
-            raise XdeError("xde_ctrl_params_t layout mismatch between header and ctypes mirror")
-        if lib.xde_sizeof_segments() != C.sizeof(XdeSegments):
-            raise XdeError("xde_segments_t layout mismatch between header and ctypes mirror")
+        _bind(lib)
         _lib = lib
     return _lib
 
@@ -434,7 +372,7 @@ class HipBackend:
     # solver instances on the same device and stream: odeint_adjoint's backward builds one solver per output interval, and
     # four allocations + fills each time are a measurable part of a launch-bound solve.  Reuse is stream-ordered.
     def acquire_work(self, device, state_dtype):
-        key = (device.index, state_dtype, self._stream_of(device))
+        key = (device.index, state_dtype, stream_of(device))
         pool = self._work_pool.setdefault(key, [])
         if pool:
             return pool.pop()
@@ -451,11 +389,6 @@ class HipBackend:
         pool = self._work_pool.setdefault(w.key, [])
         if len(pool) < 8:
             pool.append(w)
-
-    @staticmethod
-    def _stream_of(device):
-        idx = device.index if device.index is not None else torch.cuda.current_device()
-        return _raw_stream(idx) if _raw_stream is not None else torch.cuda.current_stream(device).cuda_stream
 
     def new_sums(self, device):
         return torch.zeros(2 * XDE_MAX_SEG, dtype=torch.float64, device=device)
@@ -604,8 +537,8 @@ class HipBackend:
         """What followed a norm pass of the initial-step heuristic as launches of its own — finalize, result, the scalar phase, and in
         phase 1 the control block's construction — as ONE one-workgroup launch (states above initial_step_fused's reach).
         ``t_start = nan`` / ``keep_seq``: as initial_step_fused.  Phase 1 (not ``keep_seq``) also publishes the constructed block to the
-        control block's host mirror: ``ctrl_init_handle(ctrl)`` is then the handle ``ctrl_wait`` takes — where the first attempt lands,
-        without a copy command on the stream (the publication takes a sequence number of its own: the slot it lands in may still
+        control block's host mirror: ``ctrl_peek_async(ctrl)`` then hands out that slot — where the first attempt lands, without
+        a copy command on the stream (the publication takes a sequence number of its own: the slot it lands in may still
         hold the previous owner's last block under the old number)."""
         self._require_device(ws, hs, ctrl, t_probe, t_span_dev, t_stage)
         m = self._mirrors.get(ctrl.data_ptr()) if (phase == 1 and not keep_seq) else None
@@ -621,14 +554,6 @@ class HipBackend:
         if m is not None:
             m.seq0 = seq0
             m.init_published = publish
-
-    def ctrl_init_handle(self, ctrl):
-        """Handle (for ``ctrl_wait``) of the freshly constructed block when the launch that constructed it published it to the host
-        mirror (initial_step_tail); else None — ``ctrl_peek_async`` enqueues a copy instead."""
-        m = self._mirrors.get(ctrl.data_ptr())
-        if m is not None and m.init_published and m.seq == m.seq0:
-            return (m, m.seq0)
-        return None
 
     def ctrl_init(self, ctrl, params, t_start, first_step, n_out, t_span_dev, step_t_dev, t_stage, first_step_dev=None, keep_seq=False):
         """``t_start = nan``: the start time is ``t_span_dev[0]``; ``keep_seq``: the block goes on counting its controller launches
@@ -699,9 +624,13 @@ class HipBackend:
         """Enqueue a copy of the control block AS IT IS AT THIS POINT OF THE STREAM into pinned host memory (a freshly constructed block
         has no mirror slot); ``ctrl_peek_result(handle)`` waits for that copy only — not for anything enqueued after it.  Re-entrant:
         every handle has a buffer and an event of its own until it is consumed; they are pooled with the block's mirror (control
-        blocks are recycled between solves), so a steady state of one peek per solve allocates nothing."""
+        blocks are recycled between solves), so a steady state of one peek per solve allocates nothing.  A block that the launch which
+        constructed it has published to the host mirror (initial_step_tail), with no controller launch since, is read from there:
+        nothing is enqueued."""
         self._require_device(ctrl)
         m = self._mirrors.get(ctrl.data_ptr())
+        if m is not None and m.init_published and m.seq == m.seq0:
+            return (m, m.seq0)
         pool = None
         if m is not None:
             if m.peek is None:
@@ -722,7 +651,7 @@ class HipBackend:
         return HipBackend._Peek(host, ev, ctrl.device, pool)
 
     def ctrl_peek_result(self, handle) -> XdeCtrl:
-        if isinstance(handle, tuple):  # ctrl_init_handle: the block is in the mirror ring
+        if isinstance(handle, tuple):  # the block is in the mirror ring
             return self.ctrl_wait(handle)
         if handle.host is None:
             raise XdeError("ctrl_peek_result: this handle has been consumed already")
@@ -766,9 +695,6 @@ class HipBackend:
         self._check(rc, "xde_scale_fanout")
 
     # -- back-propagation through the accepted steps (include/xde_hip_backprop.h) ------------------------------------------
-    def backprop_supported(self):
-        return all(hasattr(self.lib, sym) for sym in BACKPROP_SYMBOLS)
-
     def stage_cotangent(self, out, xs, coef, *, out2=None, coef2=None):
         """out = sum_j xs[j] * coef[j]  [, out2 = sum_j xs[j] * coef2[j]]: one launch, every operand read once."""
         self._require_device(out, out2, *xs)

@@ -160,18 +160,16 @@ def _pack(tensors, segs, total, dtype, device):
     """The members of a tuple state in one flat buffer (16-byte-aligned segments, pads zero).  On the device this is ONE launch
     (xde_pack_segments) instead of a fill + one copy per member — odeint_adjoint's augmented dynamics packs its 7-member result on
     every evaluation; the framework-op path stays for what the kernel does not take (mixed dtypes, strided members, members that
-    carry an autograd graph, the CPU test double)."""
+    carry an autograd graph, members off the device)."""
     scales = getattr(tensors, "scales", None)  # ScaledTuple: member s counts as tensors[s] * scales[s]
     tensors = list(tensors)
     if (torch.device(device).type == "cuda" and len(tensors) == len(segs)
             and not (torch.is_grad_enabled() and any(x.requires_grad for x in tensors))):
         from .. import _hip
 
-        be = _hip.get_backend()
-        if hasattr(be, "pack_segments"):
-            flat = torch.empty(total, dtype=dtype, device=device)
-            if be.pack_segments(flat, tensors, segs, scales):
-                return flat
+        flat = torch.empty(total, dtype=dtype, device=device)
+        if _hip.get_backend().pack_segments(flat, tensors, segs, scales):
+            return flat
     flat = torch.zeros(total, dtype=dtype, device=device)
     for i, (x, (s, n)) in enumerate(zip(tensors, segs)):
         if n:

@@ -4,6 +4,8 @@ import collections
 import numpy as np
 import torch
 
+from .. import _hip
+
 _NP = {torch.float32: np.float32, torch.float64: np.float64}
 
 
@@ -74,13 +76,14 @@ def upload_const(arr, device, stream_key=None):
     return t
 
 
-def scalar_const(value, dtype, device, stream_key=None):
+def scalar_const(value, dtype, device):
     """``scalar`` for a value func only READS (a solve's start time): the 0-dim tensor made for the same value, dtype, device and
     stream before is handed out again (a fill launch and ~10 us of host time per solve otherwise).  As with the reference, which hands
     func views of the caller's own ``t_span``, a func must not write into its time argument."""
-    if torch.device(device).type != "cuda" or torch.cuda.is_current_stream_capturing():
+    device = torch.device(device)
+    if device.type != "cuda" or torch.cuda.is_current_stream_capturing():
         return scalar(value, dtype, device)
-    key = ("scalar", float(value), dtype, torch.device(device).index, stream_key)
+    key = ("scalar", float(value), dtype, device.index, _hip.stream_of(device))
     t = _CONST_TABLES.get(key)
     if t is None:
         t = _CONST_TABLES[key] = scalar(value, dtype, device)

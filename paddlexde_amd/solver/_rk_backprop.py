@@ -37,15 +37,6 @@ from ._common import as_operand, np_dtype, t_span_to_host
 _Step = collections.namedtuple("_Step", "t0, t1, dt, ob, oe, y, f")
 
 
-def require_backend(backend):
-    """One clear error at entry when the kernels of include/xde_hip_backprop.h are not there."""
-    ok = backend.backprop_supported() if hasattr(backend, "backprop_supported") else (
-        hasattr(backend, "stage_cotangent") and hasattr(backend, "dense_cotangent"))
-    if not ok:
-        raise _hip.XdeError("paddlexde_amd: options['backprop'] = 'steps' needs xde_stage_cotangent / xde_dense_cotangent "
-                            "(include/xde_hip_backprop.h), which this build of the library does not export; rebuild it")
-
-
 def quartic_weights(x, dt):
     """Weights of (y0, y1, y_mid, f0, f1) in the dense-output quartic at fraction ``x`` (csrc/xde_dense.hip: quartic_)."""
     x2 = x * x
@@ -84,7 +75,6 @@ class StepsRun:
         xde = self._BaseODE(self.func, y0=y0, t_span=self.t_span)
         s = self.solver_cls(xde=xde, y0=xde.y0, rtol=self.rtol, atol=self.atol, pipeline="sync", _step_hook=self._hook,
                             **self.options)
-        require_backend(s.backend)
         solution = s.integrate(self.t_span)
         self.be = s.backend
         self.shape, self.sdtype, self.device = tuple(solution.shape[1:]), solution.dtype, solution.device
@@ -293,6 +283,5 @@ class StepsBackprop(torch.autograd.Function):
 
 def odeint_steps(func, y0, t_span, solver, *, rtol, atol, options, params):
     """The solve of ``options["backprop"] = "steps"`` when a gradient is wanted (see the module docstring)."""
-    require_backend(_hip.get_backend())
     run = StepsRun(func, t_span, solver, rtol, atol, options, params)
     return StepsBackprop.apply(run, y0, *params)

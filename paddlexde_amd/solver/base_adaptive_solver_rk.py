@@ -190,8 +190,6 @@ class AdaptiveRKSolver(NormReductions, AdaptiveSolver):
             plans = _PLANS[type(self)] = build_plans(self.tableau, self.mid)
         (self._n_stage, self._stage_plan, self._fsal, self._sol_plan, self._err_plan, self._mid_plan, self._fuse_err,
          self._err2_coef, self._stage_nt, self._presum) = plans
-        if not hasattr(self.backend, "stage_combine_pre"):
-            self._presum = {}
 
         # -- how the host drives the attempts (one object per pipeline, all over this stepper), and the re-armable interval solves --
         self._sync = SyncPipeline(self)
@@ -283,7 +281,7 @@ class AdaptiveRKSolver(NormReductions, AdaptiveSolver):
         self.y0 = y0 = as_operand(self.y0.detach())
         self.backend.require_device(y0)
         # f0 = move(t_span[0], t_span[1] - t_span[0], y0)                                          :83
-        self._t0_dev = scalar_const(t_span[0], self.dtype, y0.device, self.backend._stream_of(y0.device) if hasattr(self.backend, "_stream_of") else None)
+        self._t0_dev = scalar_const(t_span[0], self.dtype, y0.device)
         f0 = self._eval(self._t0_dev, y0)
         f0_dup = None
         if self.first_step is None and not self._reuse_f0 and not self._custom_norm:
@@ -311,11 +309,9 @@ class AdaptiveRKSolver(NormReductions, AdaptiveSolver):
         # constructed — on the device when the heuristic chose the step): a copy of the block is enqueued here, behind the
         # heuristic's kernels and ahead of the first attempt's, and read when the second attempt is about to be enqueued
         self._init_peek = None
-        if (hasattr(be, "ctrl_peek_async")
-                and (self.pipeline == "lag" or (self.pipeline == "auto" and self._auto.pick() == "lag"))):
-            # (the large-state heuristic's last launch has published that block to the host mirror already: nothing to enqueue)
-            h = be.ctrl_init_handle(self._ctrl) if hasattr(be, "ctrl_init_handle") else None
-            self._init_peek = h if h is not None else be.ctrl_peek_async(self._ctrl)
+        if self.pipeline == "lag" or (self.pipeline == "auto" and self._auto.pick() == "lag"):
+            # (when the large-state heuristic's last launch has published that block to the host mirror, nothing is enqueued)
+            self._init_peek = be.ctrl_peek_async(self._ctrl)
 
     def _setup(self, t_span):
         """Buffers, output times and controller parameters of a solve over ``t_span`` (everything before the first evaluation)."""
@@ -395,14 +391,14 @@ class AdaptiveRKSolver(NormReductions, AdaptiveSolver):
         """One-workgroup initial step (xde_initial_step_fused): small state, native norm in one launch's worth of segments, one GPU,
         no prescribed step sequence.  (``_fused_first`` = False keeps the separate launches: same results, the parity tests' A/B.)"""
         return (self._small_state and self._chunks is None and self.process_group is None and not self._replay
-                and hasattr(self.backend, "initial_step_fused") and self._fused_first)
+                and self._fused_first)
 
     def _tail_first_step(self):
         """The heuristic of a state above the one-workgroup kernels' reach in 4 launches instead of 12 (xde_scaled_norm2_partial,
         xde_initial_step_tail): a native norm in one launch's worth of segments, one GPU (a sharded run exchanges the sums between
         finalize and result), no prescribed step sequence.  (``_fused_first`` = False keeps the separate launches: same results.)"""
         return (not self._custom_norm and self._chunks is None and self.process_group is None and not self._replay
-                and hasattr(self.backend, "initial_step_tail") and self._fused_first)
+                and self._fused_first)
 
     def _select_initial_step_device(self, t0, y0, f0=None):
         """``select_initial_step`` (base_adaptive_solver.py:33-72) with its scalar arithmetic on the device: the three

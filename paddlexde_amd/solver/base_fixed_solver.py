@@ -143,10 +143,8 @@ class FixedSolver(metaclass=abc.ABCMeta):
         return out
 
     def _presum_ok(self, y0, ks):
-        """Whether the last stage-input launch may emit the final sum's leading terms: the backend offers it and nothing here is being
-        differentiated (the autograd node of a combine has one output).  Same bits either way."""
-        if not hasattr(self.backend, "stage_combine_pre_weighted"):
-            return False
+        """Whether the last stage-input launch may emit the final sum's leading terms: nothing here is being differentiated (the
+        autograd node of a combine has one output).  Same bits either way."""
         if self._rec is not None:
             return True  # (recording pass: the same launches, in the same order, either way)
         return not (torch.is_grad_enabled() and (y0.requires_grad or any(k.requires_grad for k in ks)))

@@ -29,9 +29,7 @@ class HistoryIndex(torch.autograd.Function):
         out_shape = tuple(his_c.shape[:-2]) + (lags_c.numel(), his_c.shape[-1])
         y_lags = torch.empty(out_shape, dtype=dtype, device=his.device)
         derivative_lags = torch.empty_like(y_lags)
-        if interp_method == "cubic" or not hasattr(be, "history_gather"):
-            if interp_method != "cubic":
-                raise NotImplementedError("this backend serves the cubic history spline only")
+        if interp_method == "cubic":
             be.hermite_gather(y_lags, derivative_lags, his_c, t_c, lags_c)
         else:
             need = 2 if interp_method == "linear" else 4
@@ -47,8 +45,7 @@ class HistoryIndex(torch.autograd.Function):
     def backward(ctx, grad_y):
         (derivative_lags,) = ctx.saved_tensors
         be = _hip.get_backend()
-        if (hasattr(be, "lag_grad") and grad_y.dtype == derivative_lags.dtype and grad_y.shape == derivative_lags.shape
-                and derivative_lags.shape[-2] <= 2048):
+        if grad_y.dtype == derivative_lags.dtype and grad_y.shape == derivative_lags.shape and derivative_lags.shape[-2] <= 2048:
             # one launch: sum over every axis but the lag axis (xde_lag_grad serves every row length D and alignment; up to 2048 lags)
             grad = be.lag_grad(grad_y.contiguous(), derivative_lags)
         else:

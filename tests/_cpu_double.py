@@ -496,6 +496,9 @@ class NumpyDoubleBackend:
             c.next_step_index += 1
         self._plan_next(c, p, None if step_t_dev is None else step_t_dev.numpy(), t_stage)
 
+    def p2p_rk_control(self, ctrl, params, ws, exchange, t_span_dev, step_t_dev, t_stage):
+        raise _hip.XdeError("the numpy double has no peer-to-peer transport")
+
     def ctrl_read(self, ctrl) -> XdeCtrl:
         return XdeCtrl.from_buffer_copy(ctrl.numpy().tobytes())
 
@@ -558,6 +561,36 @@ class NumpyDoubleBackend:
         gv = _np(g).reshape(-1)
         for o, f in zip(outs, factors):
             _np(o).reshape(-1)[...] = gv * (T(f) * dt)
+
+    # -- back-propagation through the accepted steps (include/xde_hip_backprop.h, same op order as csrc/xde_backprop.hip) -------
+    def stage_cotangent(self, out, xs, coef, *, out2=None, coef2=None):
+        assert 1 <= len(xs) <= _hip.XDE_BP_MAX_X
+        self.launches.append("cotangent")
+        T = _NP[out.dtype]
+        xv = [x.detach().numpy().reshape(-1) for x in xs]
+        for o, cs in ((out, coef), (out2, coef2)):
+            if o is None:
+                continue
+            s = xv[0] * T(cs[0])
+            for x, c in zip(xv[1:], cs[1:]):
+                s = s + x * T(c)
+            o.detach().numpy().reshape(-1)[...] = s
+
+    def dense_cotangent(self, outs, g_rows, weights, acc_mask=0):
+        self.launches.append("dense_cotangent")
+        T = _NP[g_rows.dtype]
+        G = len(weights)
+        g = g_rows.detach().numpy().reshape(G, -1)
+        for k, o in enumerate(outs):
+            if o is None:
+                continue
+            ov = o.detach().numpy().reshape(-1)
+            s = g[0] * T(weights[0][k])
+            if (acc_mask >> k) & 1:
+                s = ov + s
+            for r in range(1, G):
+                s = s + g[r] * T(weights[r][k])
+            ov[...] = s
 
     def hermite_gather(self, val, der, his, his_t, lags):
         self.launches.append("hermite")
@@ -639,6 +672,9 @@ class NumpyDoubleBackend:
         axes = tuple(a for a in range(g.ndim) if a != g.ndim - 2)
         return torch.from_numpy(g.sum(axis=axes).astype(_NP[der.dtype]))
 
+    def pack_segments(self, flat, tensors, segs, scales=None):
+        return False  # (not taken: the caller packs with framework ops)
+
     def dense_commit(self, out_base, ks, mid, y0, y1, f1, ctrl, t_span_dev, time_dtype):
         self.dense_eval(out_base, ks, mid, y0, y1, f1, ctrl, t_span_dev, time_dtype)
         self.commit(ctrl, y0, y1, ks[0], f1)
@@ -667,7 +703,7 @@ class NumpyDoubleBackend:
         # the double executes ops immediately: "capture" records the callable, each replay runs it
         return NumpyDoubleBackend._Replayable(self, body, ctrl, launches)
 
-    def prof_enable(self, on=True):
+    def prof_enable(self, period=1):
         pass
 
     def prof_collect(self):

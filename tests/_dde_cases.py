@@ -120,8 +120,6 @@ def test_lag_gradient_reduction_at_odd_sizes(dev, dtype):
     from paddlexde_amd import _hip
 
     be = _hip.get_backend()
-    if not hasattr(be, "lag_grad"):
-        pytest.skip("backend without lag_grad")
     rng = np.random.RandomState(3)
     # (the last rows: ADVICE r04 — rows longer than a workgroup's reach, D > 1024 for fp32 / > 512 for fp64, were refused by the C entry
     # point while the Python gate let them through; an [L, D] plane of exactly 256 vectors; more lags than one workgroup has lanes)

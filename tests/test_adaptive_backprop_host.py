@@ -5,63 +5,17 @@ import importlib
 import warnings
 import weakref
 
-import numpy as np
 import pytest
 import torch
 
 from paddlexde_amd import AdaptiveHeun, Bosh3, Dopri5, Dopri8, Fehlberg2, RK4, _hip, odeint
 from paddlexde_amd.utils.ode_utils import _rms_norm
 
-from . import _cpu_double
 from ._backprop_twin import twin_odeint
 
 odeint_mod = importlib.import_module("paddlexde_amd.functional.odeint")
 
 SOLVERS = [(Dopri5, "dopri5"), (Dopri8, "dopri8"), (Bosh3, "bosh3"), (Fehlberg2, "fehlberg2"), (AdaptiveHeun, "adaptive_heun")]
-_NP = {torch.float32: np.float32, torch.float64: np.float64}
-
-
-class BackpropDouble(_cpu_double.NumpyDoubleBackend):
-    """The numpy double plus the contracts of include/xde_hip_backprop.h (same op order as csrc/xde_backprop.hip)."""
-
-    def stage_cotangent(self, out, xs, coef, *, out2=None, coef2=None):
-        assert 1 <= len(xs) <= _hip.XDE_BP_MAX_X
-        self.launches.append("cotangent")
-        T = _NP[out.dtype]
-        xv = [x.detach().numpy().reshape(-1) for x in xs]
-        for o, cs in ((out, coef), (out2, coef2)):
-            if o is None:
-                continue
-            s = xv[0] * T(cs[0])
-            for x, c in zip(xv[1:], cs[1:]):
-                s = s + x * T(c)
-            o.detach().numpy().reshape(-1)[...] = s
-
-    def dense_cotangent(self, outs, g_rows, weights, acc_mask=0):
-        self.launches.append("dense_cotangent")
-        T = _NP[g_rows.dtype]
-        G = len(weights)
-        g = g_rows.detach().numpy().reshape(G, -1)
-        for k, o in enumerate(outs):
-            if o is None:
-                continue
-            ov = o.detach().numpy().reshape(-1)
-            s = g[0] * T(weights[0][k])
-            if (acc_mask >> k) & 1:
-                s = ov + s
-            for r in range(1, G):
-                s = s + g[r] * T(weights[r][k])
-            ov[...] = s
-
-
-@pytest.fixture
-def bp_double():
-    be = BackpropDouble()
-    _hip._set_backend_for_testing(be)
-    try:
-        yield be
-    finally:
-        _hip._set_backend_for_testing(None)
 
 
 class MLP(torch.nn.Module):
@@ -165,14 +119,7 @@ def test_key_absent_still_routes_to_the_adjoint_with_one_warning(monkeypatch):
     assert not [w for w in rec if "odeint_adjoint" in str(w.message)]
 
 
-def test_missing_entry_points_is_one_clear_error(cpu_double):
-    f = MLP()
-    y0 = torch.ones(2, 4, dtype=torch.float64, requires_grad=True)
-    with pytest.raises(_hip.XdeError, match="xde_stage_cotangent"):
-        odeint(f, y0, torch.tensor([0.0, 1.0], dtype=torch.float64), Dopri5, options={"norm": _rms_norm, "backprop": "steps"})
-
-
-def test_steps_without_a_gradient_is_a_plain_solve(bp_double):
+def test_steps_without_a_gradient_is_a_plain_solve(cpu_double):
     f = MLP()
     y0 = torch.ones(3, 4, dtype=torch.float64)
     t = torch.tensor(T_OUT, dtype=torch.float64)
@@ -185,10 +132,10 @@ def test_steps_without_a_gradient_is_a_plain_solve(bp_double):
     with torch.no_grad():
         out = odeint(f, y0.clone().requires_grad_(), t, Dopri5, options={"norm": _rms_norm, "backprop": "steps"})
     assert out.grad_fn is None and torch.equal(out, ref)
-    assert "cotangent" not in bp_double.launches
+    assert "cotangent" not in cpu_double.launches
 
 
-def test_steps_with_a_fixed_solver_is_accepted(bp_double):
+def test_steps_with_a_fixed_solver_is_accepted(cpu_double):
     f = MLP()
     y0 = torch.ones(3, 4, dtype=torch.float64, requires_grad=True)
     t = torch.tensor([0.0, 0.5, 1.0], dtype=torch.float64)
@@ -200,7 +147,7 @@ def test_steps_with_a_fixed_solver_is_accepted(bp_double):
 # -- the sweep against the twin ---------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("solver,name", SOLVERS, ids=[n for _, n in SOLVERS])
 @pytest.mark.parametrize("problem", ["mlp", "linear"])
-def test_sweep_matches_the_twin_fp64(bp_double, solver, name, problem):
+def test_sweep_matches_the_twin_fp64(cpu_double, solver, name, problem):
     f = MLP() if problem == "mlp" else Linear()
     y0 = torch.linspace(-1.0, 1.0, 12, dtype=torch.float64).reshape(3, 4)
     t = torch.tensor(T_OUT, dtype=torch.float64)
@@ -213,7 +160,7 @@ def test_sweep_matches_the_twin_fp64(bp_double, solver, name, problem):
         assert rel(a, b) <= 1e-12, (name, rel(a, b))
 
 
-def test_sweep_reverse_time_fp64(bp_double):
+def test_sweep_reverse_time_fp64(cpu_double):
     f = MLP()
     y0 = torch.linspace(-1.0, 1.0, 12, dtype=torch.float64).reshape(3, 4)
     t = torch.tensor([1.6, 1.5, 1.45, 0.7, 0.0], dtype=torch.float64)
@@ -223,7 +170,7 @@ def test_sweep_reverse_time_fp64(bp_double):
         assert rel(a, b) <= 1e-12
 
 
-def test_sweep_recomputes_the_forward_bit_for_bit(bp_double):
+def test_sweep_recomputes_the_forward_bit_for_bit(cpu_double):
     f = MLP()
     seen = []
     y0 = torch.linspace(-1.0, 1.0, 12, dtype=torch.float64).reshape(3, 4)
@@ -234,7 +181,7 @@ def test_sweep_recomputes_the_forward_bit_for_bit(bp_double):
         assert seen and all(seen)
 
 
-def test_nothing_of_the_solve_outlives_backward_without_the_cycle_collector(bp_double):
+def test_nothing_of_the_solve_outlives_backward_without_the_cycle_collector(cpu_double):
     """Every tensor an attempt made is released by reference counting alone once backward() has run and the result is gone (the
     stepper is a reference cycle: it must not be what keeps them)."""
     f = MLP()

@@ -3,6 +3,7 @@ the ctypes mirrors of the ABI structs have the header's layout.  No compute call
 import ctypes as C
 import os
 import re
+import types
 
 import pytest
 
@@ -42,6 +43,48 @@ def test_struct_layouts_match():
     for name, val in [("XDE_MAX_K", _hip.XDE_MAX_K), ("XDE_MAX_SEG", _hip.XDE_MAX_SEG), ("XDE_MAX_STAGE", _hip.XDE_MAX_STAGE),
                       ("XDE_MIRROR_SLOTS", _hip.XDE_MIRROR_SLOTS)]:
         assert int(re.search(r"#define {}\s+(\d+)".format(name), src).group(1)) == val
+
+
+def _fake_library(*, abi=_hip.ABI_VERSION, missing=()):
+    """A stand-in for the CDLL: every entry point the binding declares, as a small Python function (the queries answer what a library
+    of this build would), less the symbols in ``missing``."""
+    answers = {"xde_abi_version": abi, "xde_sizeof_ctrl": C.sizeof(_hip.XdeCtrl), "xde_sizeof_ctrl_params": C.sizeof(_hip.XdeCtrlParams),
+               "xde_sizeof_segments": C.sizeof(_hip.XdeSegments), "xde_last_error": b""}
+    return types.SimpleNamespace(**{sym: (lambda v: lambda *a: v)(answers.get(sym, 0))
+                                    for sym in _hip.SYMBOLS + _hip.BACKPROP_SYMBOLS if sym not in missing})
+
+
+def test_bind_checks_the_abi_version_before_any_other_symbol():
+    lib = types.SimpleNamespace(xde_last_error=lambda: b"", xde_abi_version=lambda: _hip.ABI_VERSION + 1)  # (nothing else exported)
+    with pytest.raises(_hip.XdeError, match="ABI version mismatch") as e:
+        _hip._bind(lib)
+    msg = str(e.value)
+    assert "version {}".format(_hip.ABI_VERSION + 1) in msg and "version {}".format(_hip.ABI_VERSION) in msg
+    assert "python -m paddlexde_amd.csrc.build --force" in msg
+
+
+def test_bind_refuses_a_library_without_an_entry_point_at_load():
+    _hip._bind(_fake_library())
+    with pytest.raises(_hip.XdeError, match="xde_stage_cotangent") as e:
+        _hip._bind(_fake_library(missing=("xde_stage_cotangent",)))
+    assert "rebuild" in str(e.value)
+
+
+def test_the_test_double_implements_the_backend_contract():
+    """The host-logic tests drive the product through tests/_cpu_double.py: it offers every public method of HipBackend with the same
+    parameters, so the product calls the backend without asking what it has."""
+    import inspect
+
+    from . import _cpu_double
+
+    def contract(cls):
+        return {n: list(inspect.signature(f).parameters.values()) for n, f in inspect.getmembers(cls, inspect.isfunction)
+                if not n.startswith("_")}
+
+    hip, double = contract(_hip.HipBackend), contract(_cpu_double.NumpyDoubleBackend)
+    assert sorted(hip) == sorted(double)
+    for name in hip:
+        assert hip[name] == double[name], (name, hip[name], double[name])
 
 
 def test_argument_validation_without_gpu():
