@@ -178,8 +178,16 @@ BACKPROP_PROTOTYPES = {
     "xde_stage_cotangent": (_i32, [_vp, _vp, _vpp, _dp, _dp, _i32, _i64, _i32, _vp]),
     "xde_dense_cotangent": (_i32, [_vpp, _vp, _dp, _i32, C.c_uint32, _i64, _i32, _vp]),
 }
+# the entry points of include/xde_hip_grid.h (the fixed-step solvers' sub-stepping); bound by load_library() after _bind
+GRID_PROTOTYPES = {
+    "xde_interp_rows": (_i32, [_vpp, C.POINTER(C.c_int), _dp, _i32, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i64, _i32, _vp]),
+}
 SYMBOLS = tuple(PROTOTYPES)
 BACKPROP_SYMBOLS = tuple(BACKPROP_PROTOTYPES)
+GRID_SYMBOLS = tuple(GRID_PROTOTYPES)
+XDE_INTERP_MAX_ROWS = 8
+XDE_INTERP_LINEAR, XDE_INTERP_CUBIC = 0, 1
+XDE_ROW_INTERP, XDE_ROW_COPY_A, XDE_ROW_COPY_B = 0, 1, 2
 
 
 class _Work:
@@ -207,7 +215,7 @@ _REBUILD = "rebuild it with `python -m paddlexde_amd.csrc.build --force`"
 
 
 def _declare(lib, sym):
-    proto = PROTOTYPES.get(sym) or BACKPROP_PROTOTYPES[sym]
+    proto = PROTOTYPES.get(sym) or BACKPROP_PROTOTYPES.get(sym) or GRID_PROTOTYPES[sym]
     try:
         fn = getattr(lib, sym)
     except AttributeError:
@@ -235,6 +243,12 @@ def _bind(lib):
         _declare(lib, sym)
 
 
+def _bind_grid(lib):
+    """Declare the entry points of include/xde_hip_grid.h on ``lib`` (after ``_bind``: the ABI check comes first)."""
+    for sym in GRID_SYMBOLS:
+        _declare(lib, sym)
+
+
 def load_library():
     """dlopen libxde_hip.so and declare prototypes.  Raises if it has not been built, or is not the library this binding speaks to."""
     global _lib
@@ -250,6 +264,7 @@ def load_library():
             )
         lib = C.CDLL(LIB_PATH)
         _bind(lib)
+        _bind_grid(lib)
         _lib = lib
     return _lib
 
@@ -714,6 +729,39 @@ class HipBackend:
                                           int(acc_mask) & 0x1F, n, dtype_code(g_rows.dtype), self._stream(g_rows))
         self._check(rc, "xde_dense_cotangent")
 
+    # -- sub-stepping of the fixed-step solvers (include/xde_hip_grid.h) ---------------------------------------------------
+    def _interp_rows(self, dsts, kinds, weights, y_a, y_b, f_a=None, f_b=None):
+        """Write the output rows of one grid step: ``dsts[r]`` <- row kind ``kinds[r]`` (XDE_ROW_*) at the four weights ``weights[r]``
+        from the contiguous operands ``y_a, y_b`` (and ``f_a, f_b``: the cubic).  Every ``dsts[r]`` has ``y_a``'s shape and is either
+        contiguous or a row block ``[..., L, D]`` of a contiguous ``[..., T*L, D]`` solution, all with the same strides.  Launches of
+        XDE_INTERP_MAX_ROWS rows; each reads the operands once.
+
+        Private on purpose: the public methods of this class are a frozen contract that tests/_cpu_double.py mirrors method for method
+        (tests/test_cabi.py).  Folding this one into that contract, together with its numpy double, is a later maintainer edit; until
+        then only FixedSolver's sub-stepping path calls it."""
+        self._require_device(y_a, y_b, f_a, f_b, *dsts)
+        cubic = f_a is not None
+        outer, chunk, row_stride = _row_geometry(dsts[0], y_a)
+        for d in dsts[1:]:
+            if d.stride() != dsts[0].stride() or d.shape != dsts[0].shape:
+                raise XdeError("_interp_rows: every destination row needs the same shape and strides")
+        for x in (y_a, y_b, f_a, f_b):
+            if x is not None and (not x.is_contiguous() or x.shape != y_a.shape or x.dtype != y_a.dtype):
+                raise XdeError("_interp_rows: the operands must be contiguous tensors of one shape and dtype")
+        if y_a.numel() == 0:
+            return
+        dt = dtype_code(y_a.dtype)
+        st = self._stream(y_a)
+        M = XDE_INTERP_MAX_ROWS
+        for r0 in range(0, len(dsts), M):
+            part = dsts[r0 : r0 + M]
+            G = len(part)
+            flat = [float(w) for row in weights[r0 : r0 + M] for w in row]
+            rc = self.lib.xde_interp_rows(_ptr_array(part), (C.c_int * G)(*[int(k) for k in kinds[r0 : r0 + M]]), _dbl_array(flat), G,
+                                          y_a.data_ptr(), y_b.data_ptr(), _ptr(f_a), _ptr(f_b),
+                                          XDE_INTERP_CUBIC if cubic else XDE_INTERP_LINEAR, outer, chunk, row_stride, dt, st)
+            self._check(rc, "xde_interp_rows")
+
     def hermite_gather(self, val, der, his, his_t, lags):
         """his [..., T, D] (contiguous), his_t [T], lags [L]  ->  val, der [..., L, D]."""
         self._require_device(val, der, his, his_t, lags)
@@ -831,6 +879,26 @@ class HipBackend:
         by = (C.c_double * n)()
         self._check(self.lib.xde_prof_collect(counts, ms, by), "xde_prof_collect")
         return {KID_NAMES[i]: {"launches": int(counts[i]), "ms": float(ms[i]), "bytes": float(by[i])} for i in range(n)}
+
+
+def _row_geometry(dst, like):
+    """(outer, chunk, row_stride) of a destination row block with ``like``'s shape: contiguous, or ``[..., L, D]`` cut from a contiguous
+    ``[..., T*L, D]`` (lead dimensions that collapse into one stride)."""
+    if dst.shape != like.shape or dst.dtype != like.dtype:
+        raise XdeError("_interp_rows: a destination row has another shape or dtype than the operands")
+    n = like.numel()
+    if dst.is_contiguous():
+        return 1, n, n
+    if dst.dim() < 3 or dst.stride(-1) != 1 or dst.stride(-2) != dst.shape[-1]:
+        raise XdeError("_interp_rows: a destination row must be a [..., L, D] block of a contiguous [..., T*L, D] solution")
+    chunk = dst.shape[-1] * dst.shape[-2]
+    row_stride = dst.stride(-3)
+    for i in range(dst.dim() - 4, -1, -1):
+        if dst.shape[i] > 1 and dst.stride(i) != dst.stride(i + 1) * dst.shape[i + 1]:
+            raise XdeError("_interp_rows: the lead dimensions of a destination row do not collapse into one stride")
+    if row_stride < chunk:
+        raise XdeError("_interp_rows: destination rows overlap")
+    return n // chunk if chunk else 0, chunk, row_stride
 
 
 _backend = None

@@ -1,9 +1,11 @@
 """The fixed solvers' per-step interpolants, restated for callers (reference: paddlexde/interpolation/functional/interp_fn.py:4-20).
 
-OFF the hot path: ``FixedSolver.integrate`` evaluates its interpolant at ``t == t1`` only (its grid IS ``t_span``; the reference's
-``step_size`` / ``grid_constructor`` sub-stepping never worked), where ``linear_interp`` returns ``y1`` and the Hermite cubic
-reduces to ``y1`` — the solvers therefore never launch these (solver/base_fixed_solver.py).  They are here, as plain framework ops in the
-reference's op order, for scripts that call them directly."""
+OFF the hot path.  Without sub-stepping ``FixedSolver.integrate`` evaluates its interpolant at ``t == t1`` only (its grid IS ``t_span``),
+where ``linear_interp`` returns ``y1`` and the Hermite cubic reduces to ``y1``.  With ``step_size`` / ``grid_constructor`` the solver
+evaluates them inside a grid step with the xde_interp_rows kernel (csrc/xde_interp.hip): the weights ``(t - t0) / (t1 - t0)`` and
+``h00, h10 * dt, h01, h11 * dt`` computed on the host in the time dtype in the op order below, the sums in the order below, the
+equality branches as exact copies.  They are here, as plain framework ops in the reference's op order, for scripts that call them
+directly."""
 import torch
 
 

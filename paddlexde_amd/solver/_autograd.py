@@ -54,3 +54,43 @@ class CombineFn(torch.autograd.Function):
         if todo_o:
             ctx.backend.scale_fanout(todo_o, g, todo_f)
         return (None, None, None, None, None, None) + tuple(outs)
+
+
+class InterpRowsFn(torch.autograd.Function):
+    """The output rows of one grid step of a sub-stepped fixed-grid solve (``HipBackend._interp_rows``) as ONE autograd node: forward
+    writes the G rows into a fresh ``[G, *y_a.shape]`` tensor; backward turns the G row cotangents into the cotangents of
+    ``(y_a, y_b, f_a, f_b)`` with xde_dense_cotangent (every row is linear in them; an exact-copy row has weight 1)."""
+
+    @staticmethod
+    def forward(ctx, backend, kinds, weights, y_a, y_b, f_a, f_b):
+        cubic = f_a is not None
+        ops = [y_a.detach(), y_b.detach()] + ([f_a.detach(), f_b.detach()] if cubic else [])
+        rows = torch.empty((len(kinds),) + tuple(y_a.shape), dtype=y_a.dtype, device=y_a.device)
+        backend._interp_rows([rows[g] for g in range(len(kinds))], kinds, weights, *ops)
+        # d row / d (y_a, y_b, y_mid, f_a, f_b): the five outputs of xde_dense_cotangent (no y_mid here)
+        w5 = []
+        for k, w in zip(kinds, weights):
+            if k == _hip.XDE_ROW_COPY_A:
+                w5.append((1.0, 0.0, 0.0, 0.0, 0.0))
+            elif k == _hip.XDE_ROW_COPY_B:
+                w5.append((0.0, 1.0, 0.0, 0.0, 0.0))
+            elif cubic:
+                w5.append((float(w[0]), float(w[2]), 0.0, float(w[1]), float(w[3])))
+            else:
+                w5.append((1.0 - float(w[0]), float(w[0]), 0.0, 0.0, 0.0))
+        ctx.backend, ctx.w5 = backend, w5
+        return rows
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        need = ctx.needs_input_grad[3:7]
+        g = g.contiguous()
+        if g.data_ptr() % 16:
+            g = g.clone()
+        like = g[0]
+        outs = [torch.empty_like(like) if need[0] else None, torch.empty_like(like) if need[1] else None, None,
+                torch.empty_like(like) if need[2] else None, torch.empty_like(like) if need[3] else None]
+        if any(o is not None for o in outs):
+            ctx.backend.dense_cotangent(outs, g, ctx.w5)
+        return (None, None, None, outs[0], outs[1], outs[3], outs[4])
