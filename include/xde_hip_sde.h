@@ -1,0 +1,57 @@
+/*
+ * xde_hip_sde.h — entry points of libxde_hip.so for sdeint: Ito Euler-Maruyama steps with diagonal noise whose Brownian increments
+ * are generated inside the kernel (host side: paddlexde_amd/solver/base_fixed_solver.py, paddlexde_amd/functional/sdeint.py).
+ *
+ * Same conventions as xde_hip.h (status codes, device pointers borrowed from the caller, `stream` = hipStream_t as void*,
+ * XDE_F32 / XDE_F64).  Arguments are validated on the host before anything is enqueued.
+ *
+ * THE NOISE.  Z[e], the standard normal of element e (flat index, 0 <= e < n) at grid step k (0-based) under the 64-bit seed, is
+ *
+ *   Philox4x32-10 (Salmon et al., SC'11; rounds M0 = 0xD2511F53, M1 = 0xCD9E8D57, key bumps W0 = 0x9E3779B9, W1 = 0xBB67AE85)
+ *   key     = (seed & 0xffffffff, seed >> 32)
+ *   counter = (j & 0xffffffff, j >> 32, k, 0)          -> words w0, w1, w2, w3
+ *
+ *   fp32: j = e / 4;  u_i = ((w_i >> 8) + 1) * 2^-24                      i = 0..3, in (0, 1]
+ *         (Z[4j], Z[4j+1]) = BM(u_0, u_1),  (Z[4j+2], Z[4j+3]) = BM(u_2, u_3)
+ *   fp64: j = e / 2;  u_a = (((w1:w0) >> 11) + 1) * 2^-53,  u_b = (((w3:w2) >> 11) + 1) * 2^-53    (hi:lo = hi * 2^32 + lo)
+ *         (Z[2j], Z[2j+1]) = BM(u_a, u_b)
+ *
+ *   BM(u1, u2) = (r * cos(2 pi u2), r * sin(2 pi u2)),  r = sqrt(-2 log(u1))
+ *
+ * computed in the state dtype with the precise math library (log, sqrt, sincospi(2 u2)).  The noise of an element depends on
+ * (seed, k, e) only.  |Z| <= sqrt(48 ln 2) = 5.77 (fp32) and sqrt(106 ln 2) = 8.57 (fp64).
+ *
+ * k is a grid step, 0 <= k < 2^32.  Operands are contiguous arrays of n elements of the state dtype; dt is the step's size and
+ * s = sqrt(|dt|) rounded to the state dtype by the caller (both converted to the state dtype in the kernel).  The library is built
+ * with -ffp-contract=off: every result below is the written op order, rounded op by op.
+ */
+#ifndef XDE_HIP_SDE_H
+#define XDE_HIP_SDE_H
+
+#include "xde_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define XDE_NOISE_NORMAL 0 /* xde_sde_noise writes Z[e], e < n, in the state dtype */
+#define XDE_NOISE_BITS 1   /* xde_sde_noise writes the raw words as uint32: out[4j + i] = w_i of counter j, for 4j + i < n */
+
+/* y1 = (y0 + f * dt) + g * (s * Z).  y1 may be y0 (an in-place step); no other overlap. */
+int xde_sde_em_step(void* y1, const void* y0, const void* f, const void* g, int64_t n, double dt, double s, uint64_t seed,
+                    int64_t k, int dtype, void* stream);
+
+/* gf = gy1 * dt and gg = gy1 * (s * Z) in one launch (the cotangents of f and g; that of y0 is gy1 itself).  A null gf or gg skips
+ * that output; both null: nothing to do. */
+int xde_sde_em_backward(void* gf, void* gg, const void* gy1, int64_t n, double dt, double s, uint64_t seed, int64_t k, int dtype,
+                        void* stream);
+
+/* The generator itself (tests, diagnostics): mode XDE_NOISE_NORMAL writes the Z the two kernels above use (the same device
+ * function); XDE_NOISE_BITS writes Philox words (dtype is checked but does not change them). */
+int xde_sde_noise(void* out, int64_t n, uint64_t seed, int64_t k, int mode, int dtype, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* XDE_HIP_SDE_H */

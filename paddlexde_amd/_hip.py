@@ -182,12 +182,20 @@ BACKPROP_PROTOTYPES = {
 GRID_PROTOTYPES = {
     "xde_interp_rows": (_i32, [_vpp, C.POINTER(C.c_int), _dp, _i32, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i64, _i32, _vp]),
 }
+# the entry points of include/xde_hip_sde.h (sdeint's Euler-Maruyama steps); bound by load_library() after _bind
+SDE_PROTOTYPES = {
+    "xde_sde_em_step": (_i32, [_vp, _vp, _vp, _vp, _i64, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
+    "xde_sde_em_backward": (_i32, [_vp, _vp, _vp, _i64, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
+    "xde_sde_noise": (_i32, [_vp, _i64, C.c_uint64, _i64, _i32, _i32, _vp]),
+}
 SYMBOLS = tuple(PROTOTYPES)
 BACKPROP_SYMBOLS = tuple(BACKPROP_PROTOTYPES)
 GRID_SYMBOLS = tuple(GRID_PROTOTYPES)
+SDE_SYMBOLS = tuple(SDE_PROTOTYPES)
 XDE_INTERP_MAX_ROWS = 8
 XDE_INTERP_LINEAR, XDE_INTERP_CUBIC = 0, 1
 XDE_ROW_INTERP, XDE_ROW_COPY_A, XDE_ROW_COPY_B = 0, 1, 2
+XDE_NOISE_NORMAL, XDE_NOISE_BITS = 0, 1
 
 
 class _Work:
@@ -215,7 +223,7 @@ _REBUILD = "rebuild it with `python -m paddlexde_amd.csrc.build --force`"
 
 
 def _declare(lib, sym):
-    proto = PROTOTYPES.get(sym) or BACKPROP_PROTOTYPES.get(sym) or GRID_PROTOTYPES[sym]
+    proto = PROTOTYPES.get(sym) or BACKPROP_PROTOTYPES.get(sym) or GRID_PROTOTYPES.get(sym) or SDE_PROTOTYPES[sym]
     try:
         fn = getattr(lib, sym)
     except AttributeError:
@@ -249,6 +257,12 @@ def _bind_grid(lib):
         _declare(lib, sym)
 
 
+def _bind_sde(lib):
+    """Declare the entry points of include/xde_hip_sde.h on ``lib`` (after ``_bind``: the ABI check comes first)."""
+    for sym in SDE_SYMBOLS:
+        _declare(lib, sym)
+
+
 def load_library():
     """dlopen libxde_hip.so and declare prototypes.  Raises if it has not been built, or is not the library this binding speaks to."""
     global _lib
@@ -265,6 +279,7 @@ def load_library():
         lib = C.CDLL(LIB_PATH)
         _bind(lib)
         _bind_grid(lib)
+        _bind_sde(lib)
         _lib = lib
     return _lib
 
@@ -761,6 +776,47 @@ class HipBackend:
                                           y_a.data_ptr(), y_b.data_ptr(), _ptr(f_a), _ptr(f_b),
                                           XDE_INTERP_CUBIC if cubic else XDE_INTERP_LINEAR, outer, chunk, row_stride, dt, st)
             self._check(rc, "xde_interp_rows")
+
+    # -- sdeint's Euler-Maruyama steps (include/xde_hip_sde.h) ---------------------------------------------------------------
+    # Private for the reason _interp_rows is: the public methods are the contract tests/_cpu_double.py mirrors.  Only the fixed-step
+    # solvers' SDE path (and its autograd node) call these.
+    @staticmethod
+    def _sde_operands(who, *ts):
+        like = ts[0]
+        for x in ts:
+            if x is not None and (not x.is_contiguous() or x.shape != like.shape or x.dtype != like.dtype):
+                raise XdeError("{}: the operands must be contiguous tensors of one shape and dtype".format(who))
+
+    def _sde_em_step(self, y1, y0, f, g, dt, s, seed, k):
+        """``y1 = (y0 + f*dt) + g*(s*Z)`` with Z the normals of (``seed``, step ``k``); ``y1`` may be ``y0``.  One launch."""
+        self._require_device(y1, y0, f, g)
+        self._sde_operands("_sde_em_step", y1, y0, f, g)
+        rc = self.lib.xde_sde_em_step(y1.data_ptr(), y0.data_ptr(), f.data_ptr(), g.data_ptr(), y0.numel(), float(dt), float(s),
+                                      int(seed), int(k), dtype_code(y0.dtype), self._stream(y0))
+        self._check(rc, "xde_sde_em_step")
+
+    def _sde_em_backward(self, gf, gg, gy1, dt, s, seed, k):
+        """``gf = gy1*dt`` and ``gg = gy1*(s*Z)`` (either may be None: skipped), one launch regenerating the forward's Z."""
+        self._require_device(gf, gg, gy1)
+        self._sde_operands("_sde_em_backward", gy1, gf, gg)
+        rc = self.lib.xde_sde_em_backward(_ptr(gf), _ptr(gg), gy1.data_ptr(), gy1.numel(), float(dt), float(s), int(seed), int(k),
+                                          dtype_code(gy1.dtype), self._stream(gy1))
+        self._check(rc, "xde_sde_em_backward")
+
+    def _sde_noise(self, out, seed, k, bits=False):
+        """The generator's output for (``seed``, step ``k``) into the contiguous ``out``: the normals Z (``out``'s dtype), or with
+        ``bits`` the raw Philox words (``out`` int32 / uint32, one word per element)."""
+        self._require_device(out)
+        if not out.is_contiguous():
+            raise XdeError("_sde_noise: out must be contiguous")
+        if bits:
+            if out.element_size() != 4 or out.is_floating_point():
+                raise XdeError("_sde_noise: the words go into a 32-bit integer tensor")
+            mode, dt = XDE_NOISE_BITS, XDE_F32
+        else:
+            mode, dt = XDE_NOISE_NORMAL, dtype_code(out.dtype)
+        rc = self.lib.xde_sde_noise(out.data_ptr(), out.numel(), int(seed), int(k), mode, dt, self._stream(out))
+        self._check(rc, "xde_sde_noise")
 
     def hermite_gather(self, val, der, his, his_t, lags):
         """his [..., T, D] (contiguous), his_t [T], lags [L]  ->  val, der [..., L, D]."""

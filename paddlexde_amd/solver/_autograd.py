@@ -1,4 +1,4 @@
-"""Autograd node around xde_stage_combine for discretise-then-optimise training.
+"""Autograd nodes around the step kernels (xde_stage_combine, xde_interp_rows, xde_sde_em_step) for discretise-then-optimise training.
 
 The reference trains by back-propagating through its eager solver ops (example/ode_demo.py:51-53:
 ``pred_y = odeint(func, batch_y0, t_span, solver=RK4); loss.backward()``).  Here the forward is one combine launch
@@ -94,3 +94,30 @@ class InterpRowsFn(torch.autograd.Function):
         if any(o is not None for o in outs):
             ctx.backend.dense_cotangent(outs, g, ctx.w5)
         return (None, None, None, outs[0], outs[1], outs[3], outs[4])
+
+
+class SdeEulerFn(torch.autograd.Function):
+    """One Euler-Maruyama step ``y1 = (y0 + f*dt) + g*(s*Z)`` (``HipBackend._sde_em_step``) as an autograd node.  The node keeps
+    only ``(dt, s, seed, k)``: backward regenerates Z from the same counter in the launch that writes ``gf = gy1*dt`` and
+    ``gg = gy1*(s*Z)`` (xde_sde_em_backward); ``gy0 = gy1`` needs no launch."""
+
+    @staticmethod
+    def forward(ctx, backend, dt, s, seed, k, y0, f, g):
+        out = torch.empty_like(y0)
+        backend._sde_em_step(out, y0.detach(), f.detach(), g.detach(), dt, s, seed, k)
+        ctx.backend, ctx.meta = backend, (float(dt), float(s), int(seed), int(k))
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        need_y0, need_f, need_g = ctx.needs_input_grad[5:8]
+        g = g.contiguous()
+        if g.data_ptr() % 16:
+            g = g.clone()
+        gf = torch.empty_like(g) if need_f else None
+        gg = torch.empty_like(g) if need_g else None
+        if gf is not None or gg is not None:
+            dt, s, seed, k = ctx.meta
+            ctx.backend._sde_em_backward(gf, gg, g, dt, s, seed, k)
+        return (None, None, None, None, None, g if need_y0 else None, gf, gg)

@@ -19,8 +19,9 @@ import torch
 from .. import _hip
 from ..xde.base_dde import DDE_DAMPING, BaseDDE
 from ..xde.base_ode import BaseODE
+from ..xde.base_sde import BaseSDE
 from ..xde.base_xde import BaseXDE
-from ._autograd import CombineFn, InterpRowsFn
+from ._autograd import CombineFn, InterpRowsFn, SdeEulerFn
 from ._common import as_operand, np_dtype, storage_ptr, t_span_to_host, upload
 
 _one_third = 1 / 3
@@ -101,6 +102,8 @@ class _SubSteps:
 class FixedSolver(metaclass=abc.ABCMeta):
     order: int
 
+    steps_sde = False  # the step is a convergent scheme for Ito SDEs (a BaseSDE problem): Euler, as Euler-Maruyama
+
     graphable = True  # the step's control flow does not depend on data (False: AdamsBashforthMoulton)
     GRAPH_MIN_STEPS = 4
     AUTO_GRAPH_MIN_STEPS = 24  # pipeline="auto": steps needed to amortise a capture (~2 ms against ~100 us saved per step)
@@ -151,14 +154,28 @@ class FixedSolver(metaclass=abc.ABCMeta):
         if self._step_end_hook and pipeline == "graph":
             raise NotImplementedError("pipeline='graph' replays a captured step and cannot call xde.on_integrate_step_end; "
                                       "use pipeline='sync' (or the default 'auto', which then keeps the eager loop)")
-        # the wrapper's fuse is what xde_stage_combine computes: BaseODE's `dy*dt + y0` or BaseDDE's damped form
+        # the wrapper's fuse is what xde_stage_combine computes: BaseODE's `dy*dt + y0` or BaseDDE's damped form; BaseSDE's
+        # Euler-Maruyama update is xde_sde_em_step
         fuse_impl = getattr(type(xde), "fuse", None)
-        if fuse_impl is BaseODE.fuse:
+        self._sde = fuse_impl is BaseSDE.fuse
+        self._k = None  # SDE: the 0-based grid step of the walk (the generator's counter) while integrate() drives step()
+        if self._sde:
+            if not self.steps_sde:
+                raise NotImplementedError("{} does not step SDEs: its tableau does not converge for Ito SDEs; use Euler "
+                                          "(Euler-Maruyama)".format(type(self).__name__))
+            if pipeline == "graph":
+                raise NotImplementedError("pipeline='graph' replays one captured step, which cannot advance the SDE's grid-step "
+                                          "counter; use pipeline='sync' (or the default 'auto', which keeps the eager loop for SDEs)")
+            if interp == "cubic":
+                raise NotImplementedError("interp='cubic' needs the derivative at both ends of a step, which an SDE path does not "
+                                          "have; use interp='linear'")
+            self._damping = 0.0
+        elif fuse_impl is BaseODE.fuse:
             self._damping = 0.0
         elif fuse_impl is BaseDDE.fuse:
             self._damping = DDE_DAMPING
         else:
-            raise NotImplementedError("only BaseODE.fuse / BaseDDE.fuse are mapped onto the HIP combine kernel")
+            raise NotImplementedError("only BaseODE.fuse / BaseDDE.fuse / BaseSDE.fuse are mapped onto the HIP kernels")
 
         self.backend = _hip.get_backend()
         self.nfe = 0
@@ -201,6 +218,21 @@ class FixedSolver(metaclass=abc.ABCMeta):
             out = torch.empty_like(y0)
         self.backend.stage_combine(out, y0, ks, coef, mode, scale=scale, dt_host=float(dt), damping=damp, out2=part, coef2=emit)
         return out if emit is None else (out, part)
+
+    def _em_step(self, t0, dtt, y0, dt):
+        """One Ito Euler-Maruyama step of a BaseSDE: ``y1 = (y0 + f*dt) + g*(s*Z)``, ``s = sqrt(|dt|)`` in the state dtype, Z the
+        normals of (xde.seed, grid step k) — one xde_sde_em_step launch (SdeEulerFn when an operand is differentiated).  Returns
+        ``(y1, f)``."""
+        self.nfe += 1
+        f, g = self.move(t0, dtt, y0)
+        f, g = as_operand(f, like=y0), as_operand(g, like=y0)
+        s = np_dtype(y0.dtype)(np.sqrt(abs(np.float64(dt))))
+        k = self._k if self._k is not None else 0  # (a step() call outside integrate() is the first step of a walk)
+        if torch.is_grad_enabled() and (y0.requires_grad or f.requires_grad or g.requires_grad):
+            return SdeEulerFn.apply(self.backend, float(dt), float(s), self.xde.seed, k, y0, f, g), f
+        out = self._y1_out if self._y1_out is not None else torch.empty_like(y0)
+        self.backend._sde_em_step(out, y0, f, g, float(dt), float(s), self.xde.seed, k)
+        return out, f
 
     def _combine_pre(self, y0, pre, ks, coef, dt, scale, out=None):
         """The final weighted sum with its leading terms pre-summed (xde_stage_combine_pre_weighted): reads y0, ``pre`` and the newest
@@ -294,7 +326,7 @@ class FixedSolver(metaclass=abc.ABCMeta):
         # pipeline="graph": one captured step replayed over the grid (no autograd, data-independent step).  "auto" (default)
         # takes it for inference-style calls (grad mode off) on small states with enough steps to pay for the capture, behind
         # the capture guard, and falls back to the eager loop below if the capture is refused or fails.
-        can_graph = (self.graphable and not self._step_end_hook and not tracking and not torch.is_grad_enabled() and table is not None and y0.is_cuda
+        can_graph = (self.graphable and not self._sde and not self._step_end_hook and not tracking and not torch.is_grad_enabled() and table is not None and y0.is_cuda
                      and self.interp != "cubic" and pred_len - 1 >= self.GRAPH_MIN_STEPS
                      and threading.current_thread() is threading.main_thread() and not torch.cuda.is_current_stream_capturing())
         if self.pipeline == "graph" and can_graph:
@@ -313,6 +345,7 @@ class FixedSolver(metaclass=abc.ABCMeta):
                 t0, t1 = t_dev[i - 1 : i], t_dev[i : i + 1]
                 self._dt = t_host[i] - t_host[i - 1]
                 self._t0_host = t_host[i - 1]
+                self._k = i - 1
                 self._row = table[i - 1] if table is not None else None
                 dst = out.narrow(-2, i * L, L)
                 self._y1_out = dst.view(y0.shape) if (direct and dst.data_ptr() % 16 == 0) else None
@@ -336,6 +369,7 @@ class FixedSolver(metaclass=abc.ABCMeta):
             self._t0_host = None
             self._row = None
             self._y1_out = None
+            self._k = None
         return out
 
     # -- sub-stepping: step_size / grid_constructor ------------------------------------------------------------------------------
@@ -384,7 +418,7 @@ class FixedSolver(metaclass=abc.ABCMeta):
                 out.narrow(-2, j * L, L).copy_(y0)
             return out
 
-        can_graph = (self.graphable and not self._step_end_hook and not tracking and not torch.is_grad_enabled() and table is not None and y0.is_cuda
+        can_graph = (self.graphable and not self._sde and not self._step_end_hook and not tracking and not torch.is_grad_enabled() and table is not None and y0.is_cuda
                      and self.interp != "cubic" and n_steps >= self.GRAPH_MIN_STEPS
                      and threading.current_thread() is threading.main_thread() and not torch.cuda.is_current_stream_capturing())
         if self.pipeline == "graph" and can_graph:
@@ -407,6 +441,7 @@ class FixedSolver(metaclass=abc.ABCMeta):
                 t0, t1 = grid_dev[k : k + 1], grid_dev[k + 1 : k + 2]
                 self._dt = grid[k + 1] - grid[k]
                 self._t0_host = grid[k]
+                self._k = k
                 self._row = table[k]
                 rows = sub.rows[k]
                 jb = next((j for j, kind, _ in rows if kind == _hip.XDE_ROW_COPY_B), None)
@@ -435,6 +470,7 @@ class FixedSolver(metaclass=abc.ABCMeta):
             self._t0_host = None
             self._row = None
             self._y1_out = None
+            self._k = None
         return out
 
     def _write_rows(self, out, L, rows, y_a, y_b, f_a=None, f_b=None):

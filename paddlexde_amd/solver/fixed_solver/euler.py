@@ -5,6 +5,7 @@ from ..base_fixed_solver import FixedSolver
 
 class Euler(FixedSolver):
     order = 1
+    steps_sde = True  # a BaseSDE is stepped as Ito Euler-Maruyama (FixedSolver._em_step)
 
     @staticmethod
     def _time_values(dt):
@@ -13,6 +14,8 @@ class Euler(FixedSolver):
     def step(self, t0, t1, y0):
         dt = self._host_dt(t0, t1)
         (dtt,) = self._times(t0, dt)
+        if self._sde:
+            return self._em_step(t0, dtt, y0, dt)
         dy = self._f(t0, dtt, y0)
         y1 = self._combine(y0, [dy], [1.0], _hip.COMBINE_FUSE, dt, out=self._y1_out)
         return y1, dy

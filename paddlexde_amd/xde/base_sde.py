@@ -1,0 +1,66 @@
+"""Stochastic-equation problem wrapper (reference: paddlexde/xde/base_sde.py:11-61).
+
+``dy = f(t, y) dt + g(t, y) dW`` with diagonal noise: ``W`` has the state's shape and ``g(t, y)`` returns a tensor of ``y``'s shape
+and dtype that multiplies the Brownian increment element by element.  ``move`` evaluates both coefficients and ``fuse`` is the Ito
+Euler-Maruyama update ``(y0 + f*dt) + g*dW``, the step the reference meant (its ``move`` computes ``f(t0, y0)`` and
+``g(t0, y0) * I_k`` with ``I_k = bm(t0, t1)``; its ``fuse`` is marked TODO).  The fixed-step solvers never call ``fuse``: they map a
+``BaseSDE`` onto xde_sde_em_step, which forms ``dW = sqrt(|dt|) * Z`` from a counter-based generator inside the kernel (no Brownian
+object: the noise of element e at grid step k is a function of (seed, k, e) — include/xde_hip_sde.h).
+"""
+import numpy as np
+import torch
+
+from .base_xde import BaseXDE
+
+_SEED_LIMIT = 1 << 64
+
+
+def draw_seed():
+    """A 64-bit seed from torch's default CPU generator (``torch.manual_seed`` makes it repeatable)."""
+    lo, hi = (int(x) for x in torch.randint(0, 1 << 32, (2,), dtype=torch.int64))
+    return (hi << 32) | lo
+
+
+def check_seed(seed):
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
+        raise TypeError("the SDE seed must be an integer, 0 <= seed < 2**64, got {!r}".format(seed))
+    seed = int(seed)
+    if not 0 <= seed < _SEED_LIMIT:
+        raise ValueError("the SDE seed must satisfy 0 <= seed < 2**64, got {}".format(seed))
+    return seed
+
+
+class BaseSDE(BaseXDE):
+    def __init__(self, f, g, y0, t_span, reverse=False, seed=None):
+        super().__init__(name="SDE", var_nums=2, y0=y0, t_span=t_span)
+        if isinstance(y0, (tuple, list)):
+            raise NotImplementedError("BaseSDE takes a tensor y0, not a tuple: stack the members into one state tensor")
+        self.__dict__["f"] = f  # (plain attributes: see BaseXDE.__init__)
+        self.__dict__["g"] = g
+        self.__dict__["seed"] = draw_seed() if seed is None else check_seed(seed)
+        # `reverse` is accepted and has no effect, as in the reference (base_sde.py:40-41: `t_span.clip(0)`, result discarded)
+        self.init_y0(y0)
+
+    def init_y0(self, y0):
+        self.__dict__["y0"] = y0
+
+    def handle(self, h, ts):
+        pass
+
+    def move(self, t0, dt, y0):
+        """base_sde.py:43-58 — the drift and the diffusion at (t0, y0); the solver draws the increment."""
+        f = self.f(t0, y0)
+        g = self.g(t0, y0)
+        if not torch.is_tensor(g) or g.shape != y0.shape or g.dtype != y0.dtype:
+            got = "{} {}".format(tuple(g.shape), g.dtype) if torch.is_tensor(g) else type(g).__name__
+            raise ValueError("the diffusion g(t, y) must return a tensor of y's shape {} and dtype {} (diagonal noise), got {}".format(
+                tuple(y0.shape), y0.dtype, got))
+        return f, g
+
+    def fuse(self, dy, dt, y0):
+        """Euler-Maruyama: ``dy = (f, g, dW)`` -> ``(y0 + f*dt) + g*dW`` (the kernel's op order, with ``dW = s*Z``)."""
+        f, g, dw = dy
+        return (y0 + f * dt) + g * dw
+
+    def call_func(self, t, y0):
+        return self.f(t, y0)
