@@ -439,7 +439,8 @@ int xde_hermite_gather(void* val_out, void* der_out, const void* his, const void
  * [1-s, s] for the value and [-1, 1] for the derivative; XDE_HISTORY_BEZIER — BezierSpline (:207-298): rows i..i+3 (clamped at T-1)
  * with the Bernstein weights of s = (t - t_i) / (t_{i+3} - t_i).  Conventions as written in the reference's `_make_series`: every row is
  * divided by its own `scale{k+1}` (scale1 shifted right by k, first value repeated), the value is multiplied by scale1_i, the
- * derivative is not.  Linear needs T >= 2, Bezier T >= 4; at most 128 lags per launch.
+ * derivative is not.  Linear needs T >= 2, Bezier T >= 4; any number of lags (more than 128 are served in tiles of 128, one launch
+ * each; a lag's results do not depend on the tile it falls in).
  */
 #define XDE_HISTORY_CUBIC 0
 #define XDE_HISTORY_LINEAR 1

@@ -821,6 +821,8 @@ class HipBackend:
     def hermite_gather(self, val, der, his, his_t, lags):
         """his [..., T, D] (contiguous), his_t [T], lags [L]  ->  val, der [..., L, D]."""
         self._require_device(val, der, his, his_t, lags)
+        if val.numel() == 0:  # (an empty batch or no lags: nothing to write, and empty tensors have no storage to point at)
+            return
         T, D = his.shape[-2], his.shape[-1]
         outer = his.numel() // (T * D) if T * D else 0
         rc = self.lib.xde_hermite_gather(val.data_ptr(), der.data_ptr(), his.data_ptr(), his_t.data_ptr(), lags.data_ptr(), outer,
@@ -831,6 +833,8 @@ class HipBackend:
         """his [..., T, D] (contiguous), his_t [T], lags [L]  ->  val, der [..., L, D] of the history spline `method`
         ("cubic" | "linear" | "bez")."""
         self._require_device(val, der, his, his_t, lags)
+        if val.numel() == 0:
+            return
         T, D = his.shape[-2], his.shape[-1]
         outer = his.numel() // (T * D) if T * D else 0
         rc = self.lib.xde_history_gather(val.data_ptr(), der.data_ptr(), his.data_ptr(), his_t.data_ptr(), lags.data_ptr(), outer, T, D,
@@ -889,6 +893,8 @@ class HipBackend:
 
     def commit(self, ctrl, y0_dst, y1_src, f0_dst, f1_src):
         self._require_device(ctrl, y0_dst, y1_src, f0_dst, f1_src)
+        if y0_dst.numel() == 0:
+            return
         rc = self.lib.xde_commit(ctrl.data_ptr(), y0_dst.data_ptr(), y1_src.data_ptr(), f0_dst.data_ptr(), f1_src.data_ptr(),
                                  y0_dst.numel(), dtype_code(y0_dst.dtype), self._stream(y0_dst))
         self._check(rc, "xde_commit")

@@ -21,7 +21,7 @@ using namespace xde;
 
 namespace {
 
-constexpr int kHistMaxL = 128;
+constexpr int kHistMaxL = 128;  // lags per LAUNCH (the LDS table); more lags are served in tiles of this many
 
 template <typename T>
 struct RowsLag {
@@ -98,27 +98,30 @@ __device__ __forceinline__ RowsScale<T> make_scales(const T* __restrict__ ts, in
 template <typename T, int M, bool VEC>
 __global__ __launch_bounds__(kBlock) void xde_rows_gather_kernel(T* __restrict__ val, T* __restrict__ der, const T* __restrict__ his,
                                                                  const T* __restrict__ ts, const T* __restrict__ lags, int64_t outer,
-                                                                 int Tn, int D, int L) {
+                                                                 int Tn, int D, int L, int l0, int Lt) {
+  // This launch serves the lags l0 .. l0 + Lt - 1 (Lt <= kHistMaxL) of the L the outputs hold: rows l0 + l of every [L, D] plane.
+  // A lag's table entry depends on that lag alone, so its results do not depend on the tile it falls in.
   using P = Pack<T, VEC>;
   constexpr int W = P::W;
   __shared__ RowsLag<T> tab[kHistMaxL];
   __shared__ RowsScale<T> tsc[kHistMaxL];
-  for (int l = threadIdx.x; l < L; l += kBlock) {
-    RowsLag<T> r = make_lag<T, M>(ts, lags[l], Tn);
+  for (int l = threadIdx.x; l < Lt; l += kBlock) {
+    RowsLag<T> r = make_lag<T, M>(ts, lags[l0 + l], Tn);
     tab[l] = r;
     tsc[l] = make_scales<T, M>(ts, r.row[0], Tn);  // (row[0] == i)
   }
   __syncthreads();
   const int DV = D / W;
-  const int64_t total = outer * int64_t(L) * DV;
+  const int64_t total = outer * int64_t(Lt) * DV;
   const int64_t stride = int64_t(gridDim.x) * kBlock;
   const int64_t rowv = int64_t(Tn) * DV;
   for (int64_t e = int64_t(blockIdx.x) * kBlock + threadIdx.x; e < total; e += stride) {
     const int dv = int(e % DV);
-    const int l = int((e / DV) % L);
-    const int64_t o = e / (int64_t(DV) * L);
+    const int l = int((e / DV) % Lt);
+    const int64_t o = e / (int64_t(DV) * Lt);
     const RowsLag<T>& r = tab[l];
     const RowsScale<T>& q = tsc[l];
+    const int64_t at = e + (o * (L - Lt) + l0) * DV;  // ((o * L + l0 + l) * DV + dv: `e` itself when one tile holds every lag)
     const int64_t base = o * rowv + dv;
     P X[M];
 #pragma unroll
@@ -137,8 +140,8 @@ __global__ __launch_bounds__(kBlock) void xde_rows_gather_kernel(T* __restrict__
       v.v[x] = av * r.h1;  // evaluate(): result *= scale
       g.v[x] = ad;         // derivative(): no scale factor
     }
-    v.store_nt(val, e);
-    g.store_nt(der, e);
+    v.store_nt(val, at);
+    g.store_nt(der, at);
   }
 }
 
@@ -348,36 +351,39 @@ int xde_history_gather(void* val_out, void* der_out, const void* his, const void
   const int need = method == XDE_HISTORY_LINEAR ? 2 : 4;
   if (outer < 0 || T < need || D < 1 || L < 0)
     return fail(XDE_EBADARG, "xde_history_gather: bad sizes (linear needs T >= 2, bez T >= 4)");
-  if (L > kHistMaxL) return fail(XDE_EBADARG, "xde_history_gather: at most 128 lags per launch");
   if (dtype != XDE_F32 && dtype != XDE_F64) return fail(XDE_EBADARG, "xde_history_gather: bad dtype");
   if (outer == 0 || L == 0) return XDE_OK;
   const int width = dtype == XDE_F32 ? 4 : 2;
   const bool vec = (D % width) == 0 && aligned16(val_out) && aligned16(der_out) && aligned16(his);
-  const int64_t work = outer * int64_t(L) * (vec ? D / width : D);
-  int64_t blocks = (work + kBlock - 1) / kBlock;
-  if (blocks > grid_cap()) blocks = grid_cap();
   hipStream_t st = static_cast<hipStream_t>(stream);
   const double es = dtype == XDE_F32 ? 4.0 : 8.0;
-  ProfScope prof(XDE_KID_DENSE, double(need + 2) * double(outer) * L * D * es);
-  dim3 g(static_cast<unsigned>(blocks)), b(kBlock);
-#define LAUNCH_RG(TY, M)                                                                                                    \
-  do {                                                                                                                      \
-    if (vec)                                                                                                                \
-      XDE_LAUNCH((xde_rows_gather_kernel<TY, M, true>), g, b, st, prof, static_cast<TY*>(val_out), static_cast<TY*>(der_out), \
-                 static_cast<const TY*>(his), static_cast<const TY*>(his_t), static_cast<const TY*>(lags), outer, T, D, L);   \
-    else                                                                                                                    \
-      XDE_LAUNCH((xde_rows_gather_kernel<TY, M, false>), g, b, st, prof, static_cast<TY*>(val_out), static_cast<TY*>(der_out), \
-                 static_cast<const TY*>(his), static_cast<const TY*>(his_t), static_cast<const TY*>(lags), outer, T, D, L);   \
+#define LAUNCH_RG(TY, M)                                                                                                          \
+  do {                                                                                                                            \
+    if (vec)                                                                                                                      \
+      XDE_LAUNCH((xde_rows_gather_kernel<TY, M, true>), g, b, st, prof, static_cast<TY*>(val_out), static_cast<TY*>(der_out),       \
+                 static_cast<const TY*>(his), static_cast<const TY*>(his_t), static_cast<const TY*>(lags), outer, T, D, L, l0, Lt); \
+    else                                                                                                                          \
+      XDE_LAUNCH((xde_rows_gather_kernel<TY, M, false>), g, b, st, prof, static_cast<TY*>(val_out), static_cast<TY*>(der_out),      \
+                 static_cast<const TY*>(his), static_cast<const TY*>(his_t), static_cast<const TY*>(lags), outer, T, D, L, l0, Lt); \
   } while (0)
-  if (dtype == XDE_F32) {
-    if (method == XDE_HISTORY_LINEAR) LAUNCH_RG(float, 2);
-    else LAUNCH_RG(float, 4);
-  } else {
-    if (method == XDE_HISTORY_LINEAR) LAUNCH_RG(double, 2);
-    else LAUNCH_RG(double, 4);
+  // one launch per tile of at most kHistMaxL lags (the per-lag table lives in LDS); a tile writes its own rows of the outputs
+  for (int l0 = 0; l0 < L; l0 += kHistMaxL) {
+    const int Lt = L - l0 < kHistMaxL ? L - l0 : kHistMaxL;
+    const int64_t work = outer * int64_t(Lt) * (vec ? D / width : D);
+    int64_t blocks = (work + kBlock - 1) / kBlock;
+    if (blocks > grid_cap()) blocks = grid_cap();
+    ProfScope prof(XDE_KID_DENSE, double(need + 2) * double(outer) * Lt * D * es);
+    dim3 g(static_cast<unsigned>(blocks)), b(kBlock);
+    if (dtype == XDE_F32) {
+      if (method == XDE_HISTORY_LINEAR) LAUNCH_RG(float, 2);
+      else LAUNCH_RG(float, 4);
+    } else {
+      if (method == XDE_HISTORY_LINEAR) LAUNCH_RG(double, 2);
+      else LAUNCH_RG(double, 4);
+    }
+    HIP_TRY(hipGetLastError());
   }
 #undef LAUNCH_RG
-  HIP_TRY(hipGetLastError());
   return XDE_OK;
 }
 

@@ -598,8 +598,9 @@ class NumpyDoubleBackend:
         h = _np(his)
         ts = _np(his_t)
         Tn, D = h.shape[-2], h.shape[-1]
-        hh = h.reshape(-1, Tn, D)
-        v, dv = _np(val).reshape(hh.shape[0], -1, D), _np(der).reshape(hh.shape[0], -1, D)
+        outer, L = h.size // (Tn * D), lags.numel()  # (stated, not inferred with -1: an empty batch and an empty lag list are legal)
+        hh = h.reshape(outer, Tn, D)
+        v, dv = _np(val).reshape(outer, L, D), _np(der).reshape(outer, L, D)
 
         def h_at(j):
             jj = j if j < Tn - 1 else Tn - 2
@@ -635,8 +636,9 @@ class NumpyDoubleBackend:
         T = _NP[his.dtype]
         h, ts = _np(his), _np(his_t)
         Tn, D = h.shape[-2], h.shape[-1]
-        hh = h.reshape(-1, Tn, D)
-        v, dv = _np(val).reshape(hh.shape[0], -1, D), _np(der).reshape(hh.shape[0], -1, D)
+        outer, L = h.size // (Tn * D), lags.numel()
+        hh = h.reshape(outer, Tn, D)
+        v, dv = _np(val).reshape(outer, L, D), _np(der).reshape(outer, L, D)
         M, span = (2, 1) if method == "linear" else (4, 3)
 
         def scale1(j):

@@ -1,6 +1,10 @@
 """GPU parity, kernel level: every C-ABI kernel against the numpy statement of its contract
 (tests/_cpu_double.py, same op order as the reference's eager ops).  Element-wise kernels must be
-BIT-EXACT (the library is built with -ffp-contract=off); reductions agree to fp64-accumulation accuracy."""
+BIT-EXACT (the library is built with -ffp-contract=off); reductions agree to fp64-accumulation accuracy.
+
+Held in modules of their own: the history gathers and `xde_lag_grad`'s re-arm in test_gpu_history_kernels.py; `xde_scale_fanout`,
+`xde_commit`, `xde_dense_commit`, `xde_dense_eval` at many rows / 1 and 9-14 operands, `xde_ctrl_retarget` and `xde_error_ratio` in
+test_gpu_handover_kernels.py; the SDE kernels in test_gpu_sde.py; the sub-stepping rows in test_gpu_substep.py."""
 
 import numpy as np
 import pytest
