@@ -10,9 +10,12 @@ namespace xde {
 // K3: controller
 // ------------------------------------------------------------------------------------------
 template <typename TT> __device__ inline TT pow_(TT a, TT b);
-// fp32: a double-precision pow rounded once — the correctly rounded fp32 power in all but ~1e-9 of the cases, i.e. what the host's libm
-// powf returns (the reference's CPU path: `error_ratio ** exponent` on fp32 tensors, utils/ode_utils.py:96) except where libm itself
-// misrounds.  The device's own powf is 1-2 ulp off; one thread calls this once per attempt, so the cost is nil.
+// fp32: a double-precision pow rounded once — the correctly rounded fp32 power in all but ~2^-29 of the cases.  The host's libm powf
+// (the reference's CPU path: `error_ratio ** exponent` on fp32 tensors, utils/ode_utils.py:96) is NOT that: glibc's powf, reached through
+// numpy's scalar `float32 ** float32` on an x86-64 host, returns another float32 for about 6e-4 of the ratios (172 to 209 of 300 000
+// random ratios, for each of the exponents 1/5, 1/3, 1/8 and 0.17; numpy's vectorised `power` for about 21%).  A free-running fp32
+// comparison with the host therefore parts by an ulp roughly every 1 600 unclamped attempts (the controller tests script only ratios
+// where the two agree).  The device's own powf is 1-2 ulp off; one thread calls this once per attempt, so the cost is nil.
 template <> __device__ inline float pow_<float>(float a, float b) { return float(pow(double(a), double(b))); }
 template <> __device__ inline double pow_<double>(double a, double b) { return pow(a, b); }
 template <typename TT> __device__ inline TT fmin__(TT a, TT b);

@@ -4,7 +4,9 @@ BIT-EXACT (the library is built with -ffp-contract=off); reductions agree to fp6
 
 Held in modules of their own: the history gathers and `xde_lag_grad`'s re-arm in test_gpu_history_kernels.py; `xde_scale_fanout`,
 `xde_commit`, `xde_dense_commit`, `xde_dense_eval` at many rows / 1 and 9-14 operands, `xde_ctrl_retarget` and `xde_error_ratio` in
-test_gpu_handover_kernels.py; the SDE kernels in test_gpu_sde.py; the sub-stepping rows in test_gpu_substep.py."""
+test_gpu_handover_kernels.py; the step controller (`xde_rk_control`, `xde_error_norm_control` as a state machine, `xde_ctrl_init`,
+the block the initial-step launches construct) in test_gpu_controller_kernels.py; the SDE kernels in test_gpu_sde.py; the
+sub-stepping rows in test_gpu_substep.py."""
 
 import numpy as np
 import pytest
