@@ -27,6 +27,8 @@ from ._common import as_operand, np_dtype, storage_ptr, t_span_to_host, upload
 _one_third = 1 / 3
 _two_thirds = 2 / 3
 _one_sixth = 1 / 6
+# what rk4_alt_step_func hands to move (FixedSolver.time_values): dt, dt/3, t0 + dt/3, t0 + 2dt/3 (base_fixed_solver.py:168-174)
+RK4_ALT_TIME_VALUES = ((1.0, False), (_one_third, False), (_one_third, True), (_two_thirds, True))
 
 
 def _step_size_value(step_size):
@@ -62,14 +64,22 @@ def step_size_grid(t_host, h):
 
 
 class _SubSteps:
-    """The host plan of a sub-stepped solve, for all grid steps at once: per step, the output rows it produces —
-    ``(j, kind, (w0, w1, w2, w3))`` with ``kind`` one of ``_hip.XDE_ROW_*`` — in output order."""
+    """The host plan of a solve, for all grid steps at once: per step, the output rows it produces —
+    ``(j, kind, (w0, w1, w2, w3))`` with ``kind`` one of ``_hip.XDE_ROW_*`` — in output order.  ``grid`` None is the plain plan: the
+    grid is ``t_host`` itself and step ``k`` produces row ``k + 1`` as a copy of the step's end, whatever the times are (repeated
+    and non-monotone ones included: every interval is a step)."""
 
     def __init__(self, t_host, grid, interp):
+        self.plain = grid is None
+        if self.plain:
+            self.rows = [[(k + 1, _hip.XDE_ROW_COPY_B, (0.0, 0.0, 0.0, 0.0))] for k in range(len(t_host) - 1)]
+            self.end_row = list(range(1, len(t_host)))
+            return
         tt = t_host.dtype.type
         d = -1 if grid[-1] < grid[0] else 1
         n_steps = len(grid) - 1
         self.rows = [[] for _ in range(n_steps)]
+        self.end_row = [None] * n_steps  # per step: the output row that is a copy of the step's end (the final combine may write it)
         if n_steps == 0 or len(t_host) < 2:
             return
         tj = t_host[1:]
@@ -94,6 +104,8 @@ class _SubSteps:
                                  "(use interp='linear' or 'cubic')".format(tj[off[0]].item(), interp))
         for j in range(len(tj)):
             self.rows[int(k[j])].append((j + 1, int(kinds[j]), tuple(w[j])))
+            if kinds[j] == _hip.XDE_ROW_COPY_B and self.end_row[int(k[j])] is None:
+                self.end_row[int(k[j])] = j + 1
 
     def needs_a(self, k):
         return any(kind != _hip.XDE_ROW_COPY_B for _, kind, _ in self.rows[k])
@@ -119,9 +131,7 @@ class FixedSolver(metaclass=abc.ABCMeta):
         if pipeline not in ("auto", "sync", "lag", "graph"):
             raise ValueError("pipeline must be 'auto', 'sync' or 'graph' ('lag' means 'sync' for a fixed grid)")
         self.pipeline = pipeline
-        self._g_ctrls = None  # graph pipeline: device dt sources of the step's combines, in call order
-        self._g_slot = 0
-        self._rec = None  # recording pass: the dt every combine of a step receives, for all steps at once
+        self._arm()  # (idle)
 
         # base_fixed_solver.py:45-47 — KeyError when absent, as in the reference
         self.atol = kwargs["atol"]
@@ -158,7 +168,6 @@ class FixedSolver(metaclass=abc.ABCMeta):
         # Euler-Maruyama update is xde_sde_em_step
         fuse_impl = getattr(type(xde), "fuse", None)
         self._sde = fuse_impl is BaseSDE.fuse
-        self._k = None  # SDE: the 0-based grid step of the walk (the generator's counter) while integrate() drives step()
         if self._sde:
             if not self.steps_sde:
                 raise NotImplementedError("{} does not step SDEs: its tableau does not converge for Ito SDEs; use Euler "
@@ -179,11 +188,21 @@ class FixedSolver(metaclass=abc.ABCMeta):
 
         self.backend = _hip.get_backend()
         self.nfe = 0
-        self._dt = None  # host dt (numpy scalar of the time dtype) while integrate() drives step()
-        self._t0_host = None  # host t0 of the current step while integrate() drives step()
-        self._row = None  # current row of the uploaded time table
-        self._y1_out = None  # where the step's final combine should write (a slice of the output)
         self._tdev_cache = {}
+
+    # -- per-step state ---------------------------------------------------------------------------
+    def _arm(self, dt=None, t0_host=None, row=None, y1_out=None, k=None, ctrls=None, rec=None):
+        """The state ``step`` reads while a walk drives it, set here and nowhere else.  ``_arm()`` is the idle state, in which a
+        ``step()`` called from outside reads its times from the device: whoever arms does so inside a ``try`` whose ``finally`` is
+        ``self._arm()``, so the state is idle again also after ``func`` raised or a capture was refused."""
+        self._dt = dt  # host dt (numpy scalar of the time dtype)
+        self._t0_host = t0_host  # host t0 of the step
+        self._row = row  # the step's row of the uploaded time table
+        self._y1_out = y1_out  # where the step's final combine should write (a slice of the output, a hand-over buffer)
+        self._k = k  # SDE: the 0-based grid step of the walk (the generator's counter); None: a bare step() is step 0
+        self._g_ctrls = ctrls  # graph pipeline: device dt sources of the step's combines, in call order ...
+        self._g_slot = 0  # ... and the next one to hand out
+        self._rec = rec  # recording pass: the dt every combine of a step receives, for all steps at once
 
     # -- framework call -----------------------------------------------------------------------
     def _f(self, t, dt, y):
@@ -263,16 +282,23 @@ class FixedSolver(metaclass=abc.ABCMeta):
             return self._dt
         return np_dtype(t0.dtype)((t1 - t0).item())  # direct step() call outside integrate(): one device read
 
-    @staticmethod
-    def _time_values(dt):
-        """Host scalars (time dtype) the step hands to ``move`` besides t0/t1, in the order ``_times`` returns them."""
-        return ()
+    # per value the step hands to ``move`` besides t0 / t1, in the order ``_times`` returns them: (multiple of dt, whether the value
+    # is that offset from t0 — a stage time — or the multiple itself)
+    time_values = ()
+
+    def _time_table(self, t_host):
+        """Per step of ``t_host`` (host, time dtype): the values the step passes to ``move``, for all steps at once — element-wise
+        numpy arithmetic in the time dtype gives the values the per-step scalar expressions of ``_times`` give."""
+        dts = t_host[1:] - t_host[:-1]
+        cols = [t_host[:-1] + dts * c if offset else dts * c for c, offset in self.time_values]
+        return np.stack(cols, axis=1).astype(t_host.dtype, copy=False) if cols else np.empty((len(dts), 0), dtype=t_host.dtype)
 
     def _times(self, t0, dt):
-        vals = self._time_values(dt)
         if self._row is not None:
-            return [self._row[j : j + 1] for j in range(len(vals))]
-        return [self._tdev(v, t0) for v in vals]
+            return [self._row[j : j + 1] for j in range(len(self.time_values))]
+        # a step() outside a walk, or the cubic's extra step: constants, one device read of t0 when a value is a stage time
+        t0h = type(dt)(t0.item()) if any(offset for _, offset in self.time_values) else None
+        return [self._tdev(t0h + dt * c if offset else dt * c, t0) for c, offset in self.time_values]
 
     def _tdev(self, value, like):
         key = (float(value), like.dtype)
@@ -296,85 +322,19 @@ class FixedSolver(metaclass=abc.ABCMeta):
         self.backend.require_device(y0)
         if y0.dim() < 2:
             raise ValueError("fixed solvers concatenate on axis -2: y0 needs >= 2 dims (reference layout [..., L, D])")
-        pred_len = len(t_span)
         t_dtype = t_span.dtype if t_span.dtype in (torch.float32, torch.float64) else torch.float32
         t_host = t_span_to_host(t_span, np_dtype(t_dtype))
-        if self._substep:
-            grid = self._grid(t_host, t_span)
-            if not np.array_equal(grid, t_host):  # (a grid that IS t_span: the plain walk below, bit for bit)
-                return self._integrate_substep(t_host, grid, t_dtype)
-        # (values rounded to the time dtype on the host, as t_span.astype would; no blocking pageable copy)
-        t_dev = t_span.detach().to(device=y0.device, dtype=t_dtype) if t_span.is_cuda else upload(t_host, y0.device)
+        grid = self._grid(t_host, t_span) if self._substep else t_host
+        if grid is t_host or np.array_equal(grid, t_host):  # (a grid that IS t_span: the plain plan, bit for bit)
+            # (values rounded to the time dtype on the host, as t_span.astype would; no blocking pageable copy)
+            t_dev = t_span.detach().to(device=y0.device, dtype=t_dtype) if t_span.is_cuda else upload(t_host, y0.device)
+            return self._walk(t_host, t_dev, _SubSteps(t_host, None, self.interp), len(t_host))
+        plan = _SubSteps(t_host, grid, self.interp)  # (validated before the first launch)
+        return self._walk(grid, upload(grid, y0.device), plan, len(t_host))
 
-        # one upload: per step [t-like values the step passes to move()], computed for all steps at once (element-wise numpy
-        # arithmetic in the time dtype gives the values the per-step scalar expressions give)
-        table = None
-        if pred_len > 1:
-            dts = t_host[1:] - t_host[:-1]
-            cols = [np.broadcast_to(t_host[:-1] + v if is_time else v, dts.shape) for v, is_time in self._time_values_tagged(dts)]
-            if cols:
-                table = upload(np.stack(cols, axis=1).astype(np_dtype(t_dtype)), y0.device)
-
-        tracking = torch.is_grad_enabled() and y0.requires_grad
-        y0 = as_operand(y0 if tracking else y0.detach())
-        L, D = y0.shape[-2], y0.shape[-1]
-        lead = y0.shape[:-2]
-        out = torch.empty(*lead, pred_len * L, D, dtype=y0.dtype, device=y0.device)
-        direct = (int(np.prod(lead)) == 1) if len(lead) else True  # output rows are contiguous slices
-        out.narrow(-2, 0, L).copy_(y0)
-
-        # pipeline="graph": one captured step replayed over the grid (no autograd, data-independent step).  "auto" (default)
-        # takes it for inference-style calls (grad mode off) on small states with enough steps to pay for the capture, behind
-        # the capture guard, and falls back to the eager loop below if the capture is refused or fails.
-        can_graph = (self.graphable and not self._sde and not self._step_end_hook and not tracking and not torch.is_grad_enabled() and table is not None and y0.is_cuda
-                     and self.interp != "cubic" and pred_len - 1 >= self.GRAPH_MIN_STEPS
-                     and threading.current_thread() is threading.main_thread() and not torch.cuda.is_current_stream_capturing())
-        if self.pipeline == "graph" and can_graph:
-            return self._integrate_graph(t_host, t_dev, table, y0, out, L)
-        if (self.pipeline == "auto" and can_graph and pred_len - 1 >= self.AUTO_GRAPH_MIN_STEPS
-                and y0.numel() * y0.element_size() <= self.AUTO_GRAPH_MAX_BYTES):
-            nfe0 = self.nfe
-            try:
-                return self._integrate_graph(t_host, t_dev, table, y0, out, L, guard=True)
-            except Exception:  # refused by the guard, or func cannot be captured: eager loop, from the start
-                self.nfe = nfe0
-                self._g_ctrls = None
-
-        try:
-            for i in range(1, pred_len):
-                t0, t1 = t_dev[i - 1 : i], t_dev[i : i + 1]
-                self._dt = t_host[i] - t_host[i - 1]
-                self._t0_host = t_host[i - 1]
-                self._k = i - 1
-                self._row = table[i - 1] if table is not None else None
-                dst = out.narrow(-2, i * L, L)
-                self._y1_out = dst.view(y0.shape) if (direct and dst.data_ptr() % 16 == 0) else None
-                y1, dy0 = self.step(t0, t1, y0)
-                if self.interp == "cubic":
-                    # base_fixed_solver.py:133-137: an extra step(t1, t1, y1) supplies dy1; the Hermite cubic
-                    # evaluated at t == t1 is y1 itself (h00 = h10 = h11 = 0, h01 = 1), so only the NFE matter.
-                    self._dt = t_host[i] - t_host[i]
-                    self._t0_host = t_host[i]
-                    self._row = None
-                    self._y1_out = None
-                    self.step(t1, t1, y1)
-                # "linear": linear_interp returns y1 when t == t1 (interp_fn.py:7-8); any other value: raw y1
-                if y1.data_ptr() != dst.data_ptr():  # (differentiable copy when y1 carries an autograd graph)
-                    dst.copy_(y1)
-                if self._step_end_hook:
-                    self.on_integrate_step_end(y0, y1, t0, t1)
-                y0 = y1
-        finally:
-            self._dt = None
-            self._t0_host = None
-            self._row = None
-            self._y1_out = None
-            self._k = None
-        return out
-
-    # -- sub-stepping: step_size / grid_constructor ------------------------------------------------------------------------------
     def _grid(self, t_host, t_span):
-        """The solve's grid on the host, in the time dtype, validated (before anything runs)."""
+        """The grid of a sub-stepped solve (step_size / grid_constructor) on the host, in the time dtype, validated (before anything
+        runs)."""
         tt = t_host.dtype.type
         d = -1 if t_host[-1] < t_host[0] else 1
         if len(t_host) > 1 and np.any(d * np.diff(t_host) < 0):
@@ -390,92 +350,85 @@ class FixedSolver(metaclass=abc.ABCMeta):
             raise ValueError("grid_constructor's grid must be strictly monotone in the direction of t_span")
         return grid
 
-    def _integrate_substep(self, t_host, grid, t_dtype):
-        """The solve over ``grid`` (host, time dtype); output ``j`` is produced by the first grid step whose end has reached
-        ``t_host[j]``: an exact copy of the state at either end of the step, or the interpolant (``interp``) inside it — one
-        xde_interp_rows launch per step that produces rows (per XDE_INTERP_MAX_ROWS of them).  Steps without rows hand the state over
-        through a ping-pong pair of buffers; a row at the step's end may be written by the step's final combine directly."""
-        sub = _SubSteps(t_host, grid, self.interp)  # (validated before the first launch)
+    def _walk(self, grid, grid_dev, plan, pred_len):
+        """The solve over ``grid`` (host, time dtype; ``grid_dev`` its device copy), one step per grid interval, writing the
+        ``pred_len`` output rows ``plan`` assigns to the steps.  Plain plan: every step's end is a row, stored by the step's final
+        combine where it can write into the solution (rows that are contiguous, 16-byte aligned slices, nothing differentiated) and by
+        a copy where it cannot.  Sub-stepped plan: output ``j`` is produced by the first grid step whose end has reached its time — an
+        exact copy of the state at either end of the step, or the interpolant (``interp``) inside it — with one xde_interp_rows
+        launch per step that produces rows (per XDE_INTERP_MAX_ROWS of them); a row at the step's end may be written by the final
+        combine directly, and steps hand the state over through a ping-pong pair of buffers."""
         y0 = self.y0
-        pred_len, n_steps = len(t_host), len(grid) - 1
-        grid_dev = upload(grid, y0.device)
-        table = None
-        if n_steps > 0:
-            dts = grid[1:] - grid[:-1]
-            cols = [np.broadcast_to(grid[:-1] + v if is_time else v, dts.shape) for v, is_time in self._time_values_tagged(dts)]
-            if cols:
-                table = upload(np.stack(cols, axis=1).astype(np_dtype(t_dtype)), y0.device)
+        n_steps = len(grid) - 1
+        # one upload: per step [t-like values the step passes to move()]
+        table = upload(self._time_table(grid), y0.device) if (n_steps > 0 and self.time_values) else None
 
         tracking = torch.is_grad_enabled() and y0.requires_grad
         y0 = as_operand(y0 if tracking else y0.detach())
         L, D = y0.shape[-2], y0.shape[-1]
         lead = y0.shape[:-2]
         out = torch.empty(*lead, pred_len * L, D, dtype=y0.dtype, device=y0.device)
-        direct = (int(np.prod(lead)) == 1) if len(lead) else True
+        direct = (int(np.prod(lead)) == 1) if len(lead) else True  # output rows are contiguous slices
         out.narrow(-2, 0, L).copy_(y0)
         if n_steps == 0:  # a one-point grid (every output time is t[0]): every row is y0, as the plain walk's zero-length steps give
             for j in range(1, pred_len):
                 out.narrow(-2, j * L, L).copy_(y0)
             return out
 
+        # pipeline="graph": one captured step replayed over the grid (no autograd, data-independent step).  "auto" (default)
+        # takes it for inference-style calls (grad mode off) on small states with enough steps to pay for the capture, behind
+        # the capture guard, and falls back to the eager loop below if the capture is refused or fails.
         can_graph = (self.graphable and not self._sde and not self._step_end_hook and not tracking and not torch.is_grad_enabled() and table is not None and y0.is_cuda
                      and self.interp != "cubic" and n_steps >= self.GRAPH_MIN_STEPS
                      and threading.current_thread() is threading.main_thread() and not torch.cuda.is_current_stream_capturing())
         if self.pipeline == "graph" and can_graph:
-            return self._integrate_graph(grid, grid_dev, table, y0, out, L, sub=sub)
+            return self._integrate_graph(grid, grid_dev, table, y0, out, L, sub=plan)
         if (self.pipeline == "auto" and can_graph and n_steps >= self.AUTO_GRAPH_MIN_STEPS
                 and y0.numel() * y0.element_size() <= self.AUTO_GRAPH_MAX_BYTES):
             nfe0 = self.nfe
             try:
-                return self._integrate_graph(grid, grid_dev, table, y0, out, L, guard=True, sub=sub)
+                return self._integrate_graph(grid, grid_dev, table, y0, out, L, guard=True, sub=plan)
             except Exception:  # refused by the guard, or func cannot be captured: eager loop, from the start
                 self.nfe = nfe0
-                self._g_ctrls = None
 
         cubic = self.interp == "cubic"
-        # (a hook may keep the states it is handed, and autograd keeps them anyway: fresh ones then)
-        bufs = None if (tracking or self._step_end_hook) else (torch.empty_like(y0), torch.empty_like(y0))
+        # (the plain walk makes a state per step; a hook may keep the states it is handed, and autograd keeps them anyway)
+        bufs = None if (plan.plain or tracking or self._step_end_hook) else (torch.empty_like(y0), torch.empty_like(y0))
         y = y0
         try:
             for k in range(n_steps):
                 t0, t1 = grid_dev[k : k + 1], grid_dev[k + 1 : k + 2]
-                self._dt = grid[k + 1] - grid[k]
-                self._t0_host = grid[k]
-                self._k = k
-                self._row = table[k]
-                rows = sub.rows[k]
-                jb = next((j for j, kind, _ in rows if kind == _hip.XDE_ROW_COPY_B), None)
-                dst_b = None
-                if jb is not None and direct:
+                rows, jb = plan.rows[k], plan.end_row[k]
+                dst = dst_b = None
+                if jb is not None:
                     dst = out.narrow(-2, jb * L, L)
-                    dst_b = dst.view(y0.shape) if dst.data_ptr() % 16 == 0 else None
-                self._y1_out = dst_b if dst_b is not None else (bufs[k % 2] if bufs is not None else None)
+                    dst_b = dst.view(y0.shape) if (direct and dst.data_ptr() % 16 == 0) else None
+                y1_out = dst_b if dst_b is not None else (bufs[k % 2] if bufs is not None else None)
+                self._arm(grid[k + 1] - grid[k], grid[k], table[k] if table is not None else None, y1_out, k)
                 y1, f_a = self.step(t0, t1, y)
                 if rows:
                     f_b = None
                     if cubic:
-                        # base_fixed_solver.py:133-137: dy1 is the dy0 of step(t1, t1, y1) — only for steps that produce rows
-                        self._dt = grid[k + 1] - grid[k + 1]
-                        self._t0_host = grid[k + 1]
-                        self._row = None
-                        self._y1_out = None
+                        # base_fixed_solver.py:133-137: dy1 is the dy0 of step(t1, t1, y1) — only for steps that produce rows.  (For a
+                        # row AT t1 the Hermite cubic is y1 itself, h00 = h10 = h11 = 0 and h01 = 1: only the NFE matter then.)
+                        self._arm(dt=grid[k + 1] - grid[k + 1], t0_host=grid[k + 1], k=k)
                         _, f_b = self.step(t1, t1, y1)
-                    done = jb if (dst_b is not None and y1.data_ptr() == dst_b.data_ptr()) else None
-                    self._write_rows(out, L, [r for r in rows if r[0] != done], y, y1, f_a, f_b)
+                    if dst_b is not None and y1.data_ptr() == dst_b.data_ptr():
+                        rows = [r for r in rows if r[0] != jb]  # (the final combine wrote it)
+                    if not plan.plain:
+                        self._write_rows(out, L, rows, y, y1, f_a, f_b)
+                    elif rows:
+                        dst.copy_(y1)  # (a differentiable copy when y1 carries an autograd graph)
                 if self._step_end_hook:
                     self.on_integrate_step_end(y, y1, t0, t1)
                 y = y1
         finally:
-            self._dt = None
-            self._t0_host = None
-            self._row = None
-            self._y1_out = None
-            self._k = None
+            self._arm()
         return out
 
     def _write_rows(self, out, L, rows, y_a, y_b, f_a=None, f_b=None):
-        """Rows ``(j, kind, w)`` of one grid step into ``out`` (``[..., T*L, D]``).  Through InterpRowsFn when an operand carries an
-        autograd graph (discretise-then-optimise), else straight into the solution's layout."""
+        """Rows ``(j, kind, w)`` of one grid step of a sub-stepped plan into ``out`` (``[..., T*L, D]``).  Through InterpRowsFn when an
+        operand carries an autograd graph (discretise-then-optimise), else straight into the solution's layout."""
         if not rows:
             return
         kinds = [kind for _, kind, _ in rows]
@@ -495,23 +448,34 @@ class FixedSolver(metaclass=abc.ABCMeta):
         """The ``dt`` argument of every ``_combine`` call of one step, in call order, as arrays over all steps: ``step`` is
         run once on the ARRAY of step sizes with ``func`` and the kernels switched off (its host arithmetic is element-wise
         numpy in the time dtype, so each entry is the scalar the eager loop would pass)."""
-        self._rec, self._dt, self._t0_host = [], dts, None
-        row = torch.zeros(max(len(self._time_values(dts[:1])), 1))
-        self._row = row
+        row = torch.zeros(max(len(self.time_values), 1))
+        self._arm(dt=dts, row=row, rec=[])
         try:
             self.step(row[0:1], row[0:1], None)
             return [np.broadcast_to(np.asarray(v), dts.shape).astype(np.float64) for v in self._rec]
         finally:
-            self._rec, self._dt, self._row = None, None, None
+            self._arm()
 
-    def _integrate_graph(self, t_host, t_dev, table, y0, out, L, guard=False, sub=None):
+    def _step_body(self, row, ctrls, y_cur, y_next):
+        """One step on static buffers, as a graph replays it: the state in ``y_cur`` (the result is left there, through ``y_next``),
+        the step's times in the device ``row`` (t0, t1, the step's time values) and the dt of every combine in the control blocks
+        ``ctrls`` — the host-side dt and t0 are placeholders, nothing the kernels use derives from them."""
+        tt = np_dtype(row.dtype)
+        self._arm(dt=tt(1.0), t0_host=tt(0.0), row=row[2:], y1_out=y_next, ctrls=ctrls)
+        try:
+            y1, _ = self.step(row[0:1], row[1:2], y_cur)
+        finally:
+            self._arm()
+        y_cur.copy_(y1)
+
+    def _integrate_graph(self, t_host, t_dev, table, y0, out, L, sub, guard=False):
         """``options={"pipeline": "graph"}`` (no autograd, data-independent step): the first step runs eagerly, then ONE step
         — the combines, the framework ops of ``func``, the state hand-over — is captured into a hipGraph and replayed; per
         step the host rewrites the step's times and step sizes in device memory (two small copies) and stores the row.
         Same kernels, same operands: bit-identical to the eager loop.  For launch-latency-bound (small) states.
-        ``sub`` (sub-stepping; ``t_host`` / ``t_dev`` are then the grid): after the replay of a step that produces rows, one
-        xde_interp_rows launch outside the graph writes them from the state before the replay (one device copy) and after it."""
-        be = self.backend
+        ``t_host`` / ``t_dev`` are the grid and ``sub`` the plan: after the replay of a step the rows it produces are written outside
+        the graph — the plain plan's by a copy of the state, a sub-stepped plan's by one xde_interp_rows launch from the state before
+        the replay (one device copy) and after it."""
         dev = y0.device
         n_steps = len(t_host) - 1
         dts = t_host[1:] - t_host[:-1]
@@ -526,19 +490,17 @@ class FixedSolver(metaclass=abc.ABCMeta):
         y_cur, y_next = y0.clone(), torch.empty_like(y0)
 
         def body():
-            self._row, self._y1_out, self._g_ctrls, self._g_slot = row[2:], y_next, ctrl_list, 0
-            self._dt, self._t0_host = dts[0], t_host[0]  # placeholders: every dt the kernels use comes from `ctrls`
-            try:
-                y1, _ = self.step(row[0:1], row[1:2], y_cur)
-            finally:
-                self._row = self._y1_out = self._g_ctrls = self._dt = self._t0_host = None
-            if y1.data_ptr() != y_next.data_ptr():
-                y_next.copy_(y1)
-            y_cur.copy_(y_next)
+            self._step_body(row, ctrl_list, y_cur, y_next)
 
         def load(i):
             row.copy_(times[i])
             ctrl_dt.copy_(dt_table[i])
+
+        def store(i, y_a):
+            if sub.plain:
+                out.narrow(-2, (i + 1) * L, L).copy_(y_cur)
+            else:
+                self._write_rows(out, L, sub.rows[i], y_a, y_cur)
 
         nfe0 = self.nfe
         load(0)
@@ -551,10 +513,7 @@ class FixedSolver(metaclass=abc.ABCMeta):
                 raise RuntimeError("capture refused: func calls " + probe.hit)
         else:
             body()  # step 1, eagerly (warm-up of func and of the allocator)
-        if sub is None:
-            out.narrow(-2, L, L).copy_(y_cur)
-        else:
-            self._write_rows(out, L, sub.rows[0], y0, y_cur)
+        store(0, y0)
         per_step = self.nfe - nfe0
         from ..utils.graphed import CapturedGraph
 
@@ -563,16 +522,13 @@ class FixedSolver(metaclass=abc.ABCMeta):
             body()
         g.finish()
         self.nfe = nfe0 + per_step  # recording executes nothing
-        y_prev = torch.empty_like(y0) if sub is not None else None
+        y_prev = None if sub.plain else torch.empty_like(y0)
         for i in range(1, n_steps):
             load(i)
-            if sub is not None and sub.needs_a(i):
+            if sub.needs_a(i):
                 y_prev.copy_(y_cur)
             g.replay()
-            if sub is None:
-                out.narrow(-2, (i + 1) * L, L).copy_(y_cur)
-            else:
-                self._write_rows(out, L, sub.rows[i], y_prev, y_cur)
+            store(i, y_prev)
             self.nfe += per_step
         return out
 
@@ -593,10 +549,8 @@ class FixedSolver(metaclass=abc.ABCMeta):
 
     def _iv_host_rows(self, t_host):
         """(times row in the time dtype: t0, t1, the step's time values; the dt of every combine of the step, fp64) for one step."""
-        dts = t_host[1:] - t_host[:-1]
-        cols = [np.broadcast_to(t_host[:-1] + v if is_time else v, dts.shape) for v, is_time in self._time_values_tagged(dts)]
-        row = np.concatenate([t_host[:1], t_host[1:]] + [np.asarray(c) for c in cols]).astype(t_host.dtype)
-        return row, np.asarray([v[0] for v in self._record_combine_dts(dts)], dtype=np.float64)
+        row = np.concatenate([t_host, self._time_table(t_host)[0]])
+        return row, np.asarray([v[0] for v in self._record_combine_dts(t_host[1:] - t_host[:-1])], dtype=np.float64)
 
     def intervals_prepare(self, t_span, t_dtype, capture=True):
         """Static buffers for one-step solves, one eager step over ``t_span`` (two host times) from the constructor's ``y0`` as
@@ -631,7 +585,7 @@ class FixedSolver(metaclass=abc.ABCMeta):
                 torch.cuda.synchronize(dev)
                 g = CapturedGraph()
                 with g.capture(capture_error_mode="thread_local"):
-                    self._iv_body()
+                    self._step_body(self._iv_row, self._iv_ctrl_list, *self._iv_y)
                 g.finish()
                 self._iv_graph = g
             self.nfe = nfe0
@@ -641,17 +595,6 @@ class FixedSolver(metaclass=abc.ABCMeta):
     def interval_state(self):
         """The static state buffer a one-step solve starts from and leaves its result in."""
         return self._iv_y[0]
-
-    def _iv_body(self):
-        y_cur, y_next = self._iv_y
-        row = self._iv_row
-        self._row, self._y1_out, self._g_ctrls, self._g_slot = row[2:], y_next, self._iv_ctrl_list, 0
-        self._dt, self._t0_host = self._iv_tt(1.0), self._iv_tt(0.0)  # placeholders: every dt the kernels use comes from the block
-        try:
-            y1, _ = self.step(row[0:1], row[1:2], y_cur)
-        finally:
-            self._row = self._y1_out = self._g_ctrls = self._dt = self._t0_host = None
-        y_cur.copy_(y1)
 
     def interval_solve(self, t_span):
         """One step from ``t_span[0]`` to ``t_span[1]`` (host times) on ``interval_state``, in place; returns it."""
@@ -671,12 +614,8 @@ class FixedSolver(metaclass=abc.ABCMeta):
                 self._iv_graph.replay()
                 self.nfe += self._iv_per_step
             else:
-                self._iv_body()
+                self._step_body(self._iv_row, self._iv_ctrl_list, *self._iv_y)
         return self._iv_y[0]
-
-    def _time_values_tagged(self, dt):
-        """[(value, is_offset_from_t0)] matching ``_time_values``; default: every value is a plain dt-like."""
-        return [(v, False) for v in self._time_values(dt)]
 
     # -- base_fixed_solver.py:146-164 (classical RK4; unused by the reference's RK4 class) ------------
     def rk4_step_func(self, t0, t1, y0, f0=None):

@@ -19,7 +19,7 @@ import warnings
 import torch
 
 from ... import _hip
-from ..base_fixed_solver import FixedSolver, _one_third, _two_thirds
+from ..base_fixed_solver import RK4_ALT_TIME_VALUES, FixedSolver
 from ._adams_coeffs import bashforth, moulton
 
 _MIN_ORDER = 4
@@ -46,21 +46,7 @@ class AdamsBashforthMoulton(FixedSolver):
         self._sums = None
         self._zeros = None
 
-    # same time table as RK4 (the bootstrap steps are rk4_alt steps)
-    @staticmethod
-    def _time_values(dt):
-        return (dt, dt * _one_third, dt * _one_third, dt * _two_thirds)
-
-    def _time_values_tagged(self, dt):
-        v = self._time_values(dt)
-        return [(v[0], False), (v[1], False), (v[2], True), (v[3], True)]
-
-    def _times(self, t0, dt):
-        if self._row is not None:
-            return [self._row[j : j + 1] for j in range(4)]
-        v = self._time_values(dt)
-        t0h = type(dt)(t0.item())
-        return [self._tdev(v[0], t0), self._tdev(v[1], t0), self._tdev(t0h + v[2], t0), self._tdev(t0h + v[3], t0)]
+    time_values = RK4_ALT_TIME_VALUES  # (the bootstrap steps are rk4_alt steps)
 
     def _has_converged(self, dy_old, dy):
         """linf(|dy_old - dy| / (atol + rtol * max(|dy_old|, |dy|))) < 1 (adams.py:500-505) — one fused norm launch."""

@@ -7,9 +7,7 @@ class Euler(FixedSolver):
     order = 1
     steps_sde = True  # a BaseSDE is stepped as Ito Euler-Maruyama (FixedSolver._em_step)
 
-    @staticmethod
-    def _time_values(dt):
-        return (dt,)
+    time_values = ((1.0, False),)  # dt
 
     def step(self, t0, t1, y0):
         dt = self._host_dt(t0, t1)

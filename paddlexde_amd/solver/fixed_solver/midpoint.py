@@ -6,19 +6,7 @@ from ..base_fixed_solver import FixedSolver
 class Midpoint(FixedSolver):
     order = 2
 
-    @staticmethod
-    def _time_values(dt):
-        return (dt, 0.5 * dt, 0.5 * dt)  # dt, half_dt, t0 + half_dt
-
-    def _time_values_tagged(self, dt):
-        v = self._time_values(dt)
-        return [(v[0], False), (v[1], False), (v[2], True)]
-
-    def _times(self, t0, dt):
-        if self._row is not None:
-            return [self._row[j : j + 1] for j in range(3)]
-        v = self._time_values(dt)
-        return [self._tdev(v[0], t0), self._tdev(v[1], t0), self._tdev(type(dt)(t0.item()) + v[2], t0)]
+    time_values = ((1.0, False), (0.5, False), (0.5, True))  # dt, half_dt, t0 + half_dt
 
     def step(self, t0, t1, y0):
         dt = self._host_dt(t0, t1)
