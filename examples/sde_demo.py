@@ -2,12 +2,13 @@
 """Spiral neural-SDE demo on paddlexde_amd — counterpart of the reference's example/sde_demo.py.
 
 Data: one sample path of ``dy = 2 y A dt + y dW`` (A = [[-0.1, 2], [-2, -0.1]], diagonal noise, the reference's Lambda_f / Lambda_g)
-from y0 = [2, 0] over t in [0, 25], integrated by ``sdeint(..., solver=Euler)`` (Ito Euler-Maruyama).  Model (example/sde_demo.py:
+from y0 = [2, 0] over t in [0, 25], integrated by ``sdeint(..., solver=Euler)`` (Ito Euler-Maruyama).  ``--solver milstein`` trains
+through the strong order 1.0 Milstein steps instead (the data path stays Euler's).  Model (example/sde_demo.py:
 SDEFunc / SDEDiffusion): an MLP drift on y^3 and an MLP diffusion on y^2, both trained by back-propagating through ``sdeint`` on
 windows of ``batch_time`` points of the path (loss: mean |pred - data|).  Every call draws its own Brownian path from torch's
 generator, so ``torch.manual_seed`` makes a run repeatable.
 
-    python examples/sde_demo.py --max-steps 200
+    python examples/sde_demo.py --max-steps 200 [--solver milstein]
 """
 import argparse
 import os
@@ -20,7 +21,7 @@ import torch.nn as nn
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from paddlexde_amd.functional import sdeint  # noqa: E402
-from paddlexde_amd.solver import Euler  # noqa: E402
+from paddlexde_amd.solver import Euler, Milstein  # noqa: E402
 
 TRUE_A = [[-0.1, 2.0], [-2.0, -0.1]]
 
@@ -72,7 +73,7 @@ def get_batch(true_y, t, batch_size, batch_time, gen):
     return batch_y0, t[:batch_time], batch_y
 
 
-def train(max_steps=200, batch_size=20, batch_time=10, seed=42, device="cuda:0", log_every=50):
+def train(max_steps=200, batch_size=20, batch_time=10, seed=42, device="cuda:0", log_every=50, solver=Euler):
     torch.manual_seed(seed)
     gen = torch.Generator().manual_seed(seed)
     t, true_y = make_data(device)
@@ -82,7 +83,7 @@ def train(max_steps=200, batch_size=20, batch_time=10, seed=42, device="cuda:0",
     t0 = time.perf_counter()
     for step in range(1, max_steps + 1):
         y0, bt, by = get_batch(true_y, t, batch_size, batch_time, gen)
-        pred = sdeint(func, diffusion, y0, bt, solver=Euler)  # [B, T, 2]
+        pred = sdeint(func, diffusion, y0, bt, solver=solver)  # [B, T, 2]
         loss = torch.mean(torch.abs(pred - by))
         opt.zero_grad()
         loss.backward()
@@ -98,6 +99,7 @@ if __name__ == "__main__":
     ap.add_argument("--max-steps", type=int, default=200)
     ap.add_argument("--batch-size", type=int, default=20)
     ap.add_argument("--batch-time", type=int, default=10)
+    ap.add_argument("--solver", choices=["euler", "milstein"], default="euler")
     a = ap.parse_args()
-    ls = train(a.max_steps, a.batch_size, a.batch_time)
+    ls = train(a.max_steps, a.batch_size, a.batch_time, solver={"euler": Euler, "milstein": Milstein}[a.solver])
     print("first-10 mean loss {:.4f} -> last-10 mean loss {:.4f}".format(sum(ls[:10]) / 10, sum(ls[-10:]) / 10))

@@ -1,6 +1,6 @@
 /*
- * xde_hip_sde.h — entry points of libxde_hip.so for sdeint: Ito Euler-Maruyama steps with diagonal noise whose Brownian increments
- * are generated inside the kernel (host side: paddlexde_amd/solver/base_fixed_solver.py, paddlexde_amd/functional/sdeint.py).
+ * xde_hip_sde.h — entry points of libxde_hip.so for sdeint: Ito Euler-Maruyama and Milstein steps with diagonal noise whose Brownian
+ * increments are generated inside the kernel (host side: paddlexde_amd/solver/base_fixed_solver.py, paddlexde_amd/functional/sdeint.py).
  *
  * Same conventions as xde_hip.h (status codes, device pointers borrowed from the caller, `stream` = hipStream_t as void*,
  * XDE_F32 / XDE_F64).  Arguments are validated on the host before anything is enqueued.
@@ -46,7 +46,30 @@ int xde_sde_em_step(void* y1, const void* y0, const void* f, const void* g, int6
 int xde_sde_em_backward(void* gf, void* gg, const void* gy1, int64_t n, double dt, double s, uint64_t seed, int64_t k, int dtype,
                         void* stream);
 
-/* The generator itself (tests, diagnostics): mode XDE_NOISE_NORMAL writes the Z the two kernels above use (the same device
+/*
+ * MILSTEIN (Kloeden & Platen's explicit strong order 1.0 scheme, Ito, diagonal noise: g_i depends on y_i only).  Besides dt and s the
+ * caller passes c = 0.5 / sqrt(|dt|) rounded to the state dtype, and c = 0 when dt == 0 (a zero-length step returns y0); all three
+ * are converted to the state dtype in the kernel, and a = |dt| is taken there in the state dtype.  Z is the Z of (seed, k) above.
+ *
+ * The support point yb = (y0 + f * dt) + g * s, where the caller evaluates gb = g(t0, yb).  No generator; yb may be y0. */
+int xde_sde_milstein_support(void* yb, const void* y0, const void* f, const void* g, int64_t n, double dt, double s, int dtype,
+                             void* stream);
+
+/* gf = gyb * dt and gg = gyb * s (the cotangents of f and g at the support point; that of y0 is gyb itself).  A null gf or gg skips
+ * that output; both null: nothing to do. */
+int xde_sde_milstein_support_backward(void* gf, void* gg, const void* gyb, int64_t n, double dt, double s, int dtype, void* stream);
+
+/* w = s * Z,  q = c * (w * w - a),  y1 = ((y0 + f * dt) + g * w) + (gb - g) * q.  One launch, 5 n elements moved.  y1 may be y0; no
+ * other overlap.  The first three terms are xde_sde_em_step's expression: with gb == g the result is the EM step's, bit for bit. */
+int xde_sde_milstein_step(void* y1, const void* y0, const void* f, const void* g, const void* gb, int64_t n, double dt, double s,
+                          double c, uint64_t seed, int64_t k, int dtype, void* stream);
+
+/* gf = gy1 * dt, gg = gy1 * (w - q) and ggb = gy1 * q in one launch that regenerates Z (w and q as above; the cotangent of y0 is gy1
+ * itself).  A null output is skipped, and the generator runs only if gg or ggb is wanted; all three null: nothing to do. */
+int xde_sde_milstein_backward(void* gf, void* gg, void* ggb, const void* gy1, int64_t n, double dt, double s, double c, uint64_t seed,
+                              int64_t k, int dtype, void* stream);
+
+/* The generator itself (tests, diagnostics): mode XDE_NOISE_NORMAL writes the Z the step kernels above use (the same device
  * function); XDE_NOISE_BITS writes Philox words (dtype is checked but does not change them). */
 int xde_sde_noise(void* out, int64_t n, uint64_t seed, int64_t k, int mode, int dtype, void* stream);
 

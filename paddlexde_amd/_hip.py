@@ -182,11 +182,15 @@ BACKPROP_PROTOTYPES = {
 GRID_PROTOTYPES = {
     "xde_interp_rows": (_i32, [_vpp, C.POINTER(C.c_int), _dp, _i32, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i64, _i32, _vp]),
 }
-# the entry points of include/xde_hip_sde.h (sdeint's Euler-Maruyama steps); bound by load_library() after _bind
+# the entry points of include/xde_hip_sde.h (sdeint's Euler-Maruyama and Milstein steps); bound by load_library() after _bind
 SDE_PROTOTYPES = {
     "xde_sde_em_step": (_i32, [_vp, _vp, _vp, _vp, _i64, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
     "xde_sde_em_backward": (_i32, [_vp, _vp, _vp, _i64, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
     "xde_sde_noise": (_i32, [_vp, _i64, C.c_uint64, _i64, _i32, _i32, _vp]),
+    "xde_sde_milstein_support": (_i32, [_vp, _vp, _vp, _vp, _i64, _dbl, _dbl, _i32, _vp]),
+    "xde_sde_milstein_support_backward": (_i32, [_vp, _vp, _vp, _i64, _dbl, _dbl, _i32, _vp]),
+    "xde_sde_milstein_step": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _dbl, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
+    "xde_sde_milstein_backward": (_i32, [_vp, _vp, _vp, _vp, _i64, _dbl, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
 }
 SYMBOLS = tuple(PROTOTYPES)
 BACKPROP_SYMBOLS = tuple(BACKPROP_PROTOTYPES)
@@ -777,7 +781,7 @@ class HipBackend:
                                           XDE_INTERP_CUBIC if cubic else XDE_INTERP_LINEAR, outer, chunk, row_stride, dt, st)
             self._check(rc, "xde_interp_rows")
 
-    # -- sdeint's Euler-Maruyama steps (include/xde_hip_sde.h) ---------------------------------------------------------------
+    # -- sdeint's Euler-Maruyama and Milstein steps (include/xde_hip_sde.h) ---------------------------------------------------------------
     # Private for the reason _interp_rows is: the public methods are the contract tests/_cpu_double.py mirrors.  Only the fixed-step
     # solvers' SDE path (and its autograd node) call these.
     @staticmethod
@@ -802,6 +806,39 @@ class HipBackend:
         rc = self.lib.xde_sde_em_backward(_ptr(gf), _ptr(gg), gy1.data_ptr(), gy1.numel(), float(dt), float(s), int(seed), int(k),
                                           dtype_code(gy1.dtype), self._stream(gy1))
         self._check(rc, "xde_sde_em_backward")
+
+    def _sde_milstein_support(self, yb, y0, f, g, dt, s):
+        """Milstein's support point ``yb = (y0 + f*dt) + g*s``.  One launch, no generator."""
+        self._require_device(yb, y0, f, g)
+        self._sde_operands("_sde_milstein_support", yb, y0, f, g)
+        rc = self.lib.xde_sde_milstein_support(yb.data_ptr(), y0.data_ptr(), f.data_ptr(), g.data_ptr(), y0.numel(), float(dt), float(s),
+                                               dtype_code(y0.dtype), self._stream(y0))
+        self._check(rc, "xde_sde_milstein_support")
+
+    def _sde_milstein_support_backward(self, gf, gg, gyb, dt, s):
+        """``gf = gyb*dt`` and ``gg = gyb*s`` (either may be None: skipped), one launch."""
+        self._require_device(gf, gg, gyb)
+        self._sde_operands("_sde_milstein_support_backward", gyb, gf, gg)
+        rc = self.lib.xde_sde_milstein_support_backward(_ptr(gf), _ptr(gg), gyb.data_ptr(), gyb.numel(), float(dt), float(s),
+                                                        dtype_code(gyb.dtype), self._stream(gyb))
+        self._check(rc, "xde_sde_milstein_support_backward")
+
+    def _sde_milstein_step(self, y1, y0, f, g, gb, dt, s, c, seed, k):
+        """``y1 = ((y0 + f*dt) + g*w) + (gb - g)*q`` with ``w = s*Z``, ``q = c*(w*w - |dt|)`` and Z the normals of (``seed``, step
+        ``k``); ``y1`` may be ``y0``.  One launch."""
+        self._require_device(y1, y0, f, g, gb)
+        self._sde_operands("_sde_milstein_step", y1, y0, f, g, gb)
+        rc = self.lib.xde_sde_milstein_step(y1.data_ptr(), y0.data_ptr(), f.data_ptr(), g.data_ptr(), gb.data_ptr(), y0.numel(), float(dt),
+                                            float(s), float(c), int(seed), int(k), dtype_code(y0.dtype), self._stream(y0))
+        self._check(rc, "xde_sde_milstein_step")
+
+    def _sde_milstein_backward(self, gf, gg, ggb, gy1, dt, s, c, seed, k):
+        """``gf = gy1*dt``, ``gg = gy1*(w - q)`` and ``ggb = gy1*q`` (any may be None: skipped), one launch regenerating the forward's Z."""
+        self._require_device(gf, gg, ggb, gy1)
+        self._sde_operands("_sde_milstein_backward", gy1, gf, gg, ggb)
+        rc = self.lib.xde_sde_milstein_backward(_ptr(gf), _ptr(gg), _ptr(ggb), gy1.data_ptr(), gy1.numel(), float(dt), float(s), float(c),
+                                                int(seed), int(k), dtype_code(gy1.dtype), self._stream(gy1))
+        self._check(rc, "xde_sde_milstein_backward")
 
     def _sde_noise(self, out, seed, k, bits=False):
         """The generator's output for (``seed``, step ``k``) into the contiguous ``out``: the normals Z (``out``'s dtype), or with

@@ -1,9 +1,10 @@
-// libxde_hip.so — Ito Euler-Maruyama steps with in-kernel Brownian increments (C ABI: include/xde_hip_sde.h; host:
+// libxde_hip.so — Ito Euler-Maruyama and Milstein steps with in-kernel Brownian increments (C ABI: include/xde_hip_sde.h; host:
 // paddlexde_amd/solver/base_fixed_solver.py).
 //
 // One lane serves one Philox4x32-10 call: 4 fp32 or 2 fp64 elements, i.e. exactly one 16-byte vector of every operand.  The
-// forward reads y0, f, g once and writes y1 once (4 n elt bytes); the noise lives in registers only, and the backward regenerates it
-// from the same counter instead of reading it back.  A lane whose block runs past n (the tail), or any launch whose pointers are not
+// EM forward reads y0, f, g once and writes y1 once (4 n elt bytes), the Milstein forward reads gb as well (5 n); the noise lives in
+// registers only, and the backward regenerates it from the same counter instead of reading it back.  The Milstein support point is the
+// EM kernels with the generator compiled out (NOISE = false: s in the place of s * Z).  A lane whose block runs past n (the tail), or any launch whose pointers are not
 // all 16-byte aligned, takes the scalar path with the same bits.  Grid-stride loop over at most grid_cap() workgroups of kBlock.
 // Built with -ffp-contract=off like the rest of the library; the math functions are the precise ones (no fast-math, no __sinf).
 
@@ -80,16 +81,19 @@ __device__ __forceinline__ void normals(uint64_t j, uint32_t k, uint32_t key0, u
 struct SdeArgs {
   void* out0;       // y1 | gf | out
   void* out1;       // gg
+  void* out2;       // ggb
   const void* in0;  // y0 | gy1
   const void* in1;  // f
   const void* in2;  // g
+  const void* in3;  // gb
   int64_t n;        // elements (bits mode: words)
   int64_t nblk;     // Philox calls = lanes of work
-  double dt, s;
+  double dt, s, c;
   uint32_t key0, key1, k;
 };
 
-template <typename T, bool VEC>
+// NOISE = false is the Milstein support point yb = (y0 + f * dt) + g * s: no generator, the same loads and stores
+template <typename T, bool VEC, bool NOISE = true>
 __global__ __launch_bounds__(kBlock) void xde_sde_em_step_kernel(SdeArgs a) {
   constexpr int W = Block<T>::W;
   using P = Pack<T, true>;
@@ -105,24 +109,24 @@ __global__ __launch_bounds__(kBlock) void xde_sde_em_step_kernel(SdeArgs a) {
     if (VEC && e0 + W <= a.n) {
       const P Y = P::load(y0, j), F = P::load(f, j), G = P::load(g, j);  // (issued before the generator runs)
       T z[W];
-      normals(uint64_t(j), a.k, a.key0, a.key1, z);
+      if (NOISE) normals(uint64_t(j), a.k, a.key0, a.key1, z);
       P o;
 #pragma unroll
-      for (int v = 0; v < W; ++v) o.v[v] = (Y.v[v] + F.v[v] * dt) + G.v[v] * (s * z[v]);
+      for (int v = 0; v < W; ++v) o.v[v] = (Y.v[v] + F.v[v] * dt) + G.v[v] * (NOISE ? s * z[v] : s);
       o.store(y1, j);
     } else {
       T z[W];
-      normals(uint64_t(j), a.k, a.key0, a.key1, z);
+      if (NOISE) normals(uint64_t(j), a.k, a.key0, a.key1, z);
 #pragma unroll
       for (int v = 0; v < W; ++v) {
         const int64_t e = e0 + v;
-        if (e < a.n) y1[e] = (y0[e] + f[e] * dt) + g[e] * (s * z[v]);
+        if (e < a.n) y1[e] = (y0[e] + f[e] * dt) + g[e] * (NOISE ? s * z[v] : s);
       }
     }
   }
 }
 
-template <typename T, bool VEC, bool GF, bool GG>
+template <typename T, bool VEC, bool GF, bool GG, bool NOISE = true>
 __global__ __launch_bounds__(kBlock) void xde_sde_em_backward_kernel(SdeArgs a) {
   constexpr int W = Block<T>::W;
   using P = Pack<T, true>;
@@ -143,21 +147,115 @@ __global__ __launch_bounds__(kBlock) void xde_sde_em_backward_kernel(SdeArgs a) 
       }
       if (GG) {
         T z[W];
-        normals(uint64_t(j), a.k, a.key0, a.key1, z);
+        if (NOISE) normals(uint64_t(j), a.k, a.key0, a.key1, z);
         P o;
 #pragma unroll
-        for (int v = 0; v < W; ++v) o.v[v] = Y.v[v] * (s * z[v]);
+        for (int v = 0; v < W; ++v) o.v[v] = Y.v[v] * (NOISE ? s * z[v] : s);
         o.store(gg, j);
       }
     } else {
       T z[W];
-      if (GG) normals(uint64_t(j), a.k, a.key0, a.key1, z);
+      if (GG && NOISE) normals(uint64_t(j), a.k, a.key0, a.key1, z);
 #pragma unroll
       for (int v = 0; v < W; ++v) {
         const int64_t e = e0 + v;
         if (e < a.n) {
           if (GF) gf[e] = gy[e] * dt;
-          if (GG) gg[e] = gy[e] * (s * z[v]);
+          if (GG) gg[e] = gy[e] * (NOISE ? s * z[v] : s);
+        }
+      }
+    }
+  }
+}
+
+// w = s * Z, q = c * (w * w - |dt|), y1 = ((y0 + f * dt) + g * w) + (gb - g) * q
+template <typename T, bool VEC>
+__global__ __launch_bounds__(kBlock) void xde_sde_milstein_step_kernel(SdeArgs a) {
+  constexpr int W = Block<T>::W;
+  using P = Pack<T, true>;
+  const T dt = T(a.dt), s = T(a.s), c = T(a.c), ad = abs_(dt);
+  T* y1 = static_cast<T*>(a.out0);
+  const T* y0 = static_cast<const T*>(a.in0);
+  const T* f = static_cast<const T*>(a.in1);
+  const T* g = static_cast<const T*>(a.in2);
+  const T* gb = static_cast<const T*>(a.in3);
+  const int64_t stride = int64_t(gridDim.x) * kBlock;
+  for (int64_t j = int64_t(blockIdx.x) * kBlock + threadIdx.x; j < a.nblk; j += stride) {
+    const int64_t e0 = j * W;
+    if (VEC && e0 + W <= a.n) {
+      const P Y = P::load(y0, j), F = P::load(f, j), G = P::load(g, j), GB = P::load(gb, j);  // (issued before the generator runs)
+      T z[W];
+      normals(uint64_t(j), a.k, a.key0, a.key1, z);
+      P o;
+#pragma unroll
+      for (int v = 0; v < W; ++v) {
+        const T w = s * z[v], q = c * (w * w - ad);
+        o.v[v] = ((Y.v[v] + F.v[v] * dt) + G.v[v] * w) + (GB.v[v] - G.v[v]) * q;
+      }
+      o.store(y1, j);
+    } else {
+      T z[W];
+      normals(uint64_t(j), a.k, a.key0, a.key1, z);
+#pragma unroll
+      for (int v = 0; v < W; ++v) {
+        const int64_t e = e0 + v;
+        if (e < a.n) {
+          const T w = s * z[v], q = c * (w * w - ad);
+          y1[e] = ((y0[e] + f[e] * dt) + g[e] * w) + (gb[e] - g[e]) * q;
+        }
+      }
+    }
+  }
+}
+
+// gf = gy1 * dt, gg = gy1 * (w - q), ggb = gy1 * q
+template <typename T, bool VEC, bool GF, bool GG, bool GGB>
+__global__ __launch_bounds__(kBlock) void xde_sde_milstein_backward_kernel(SdeArgs a) {
+  constexpr int W = Block<T>::W;
+  using P = Pack<T, true>;
+  const T dt = T(a.dt), s = T(a.s), c = T(a.c), ad = abs_(dt);
+  T* gf = static_cast<T*>(a.out0);
+  T* gg = static_cast<T*>(a.out1);
+  T* ggb = static_cast<T*>(a.out2);
+  const T* gy = static_cast<const T*>(a.in0);
+  const int64_t stride = int64_t(gridDim.x) * kBlock;
+  for (int64_t j = int64_t(blockIdx.x) * kBlock + threadIdx.x; j < a.nblk; j += stride) {
+    const int64_t e0 = j * W;
+    if (VEC && e0 + W <= a.n) {
+      const P Y = P::load(gy, j);
+      if (GF) {
+        P o;
+#pragma unroll
+        for (int v = 0; v < W; ++v) o.v[v] = Y.v[v] * dt;
+        o.store(gf, j);
+      }
+      if (GG || GGB) {
+        T z[W];
+        normals(uint64_t(j), a.k, a.key0, a.key1, z);
+        P og, ob;
+#pragma unroll
+        for (int v = 0; v < W; ++v) {
+          const T w = s * z[v], q = c * (w * w - ad);
+          og.v[v] = Y.v[v] * (w - q);
+          ob.v[v] = Y.v[v] * q;
+        }
+        if (GG) og.store(gg, j);
+        if (GGB) ob.store(ggb, j);
+      }
+    } else {
+      T z[W];
+      if (GG || GGB) normals(uint64_t(j), a.k, a.key0, a.key1, z);
+#pragma unroll
+      for (int v = 0; v < W; ++v) {
+        const int64_t e = e0 + v;
+        if (e < a.n) {
+          const T y = gy[e];
+          if (GF) gf[e] = y * dt;
+          if (GG || GGB) {
+            const T w = s * z[v], q = c * (w * w - ad);
+            if (GG) gg[e] = y * (w - q);
+            if (GGB) ggb[e] = y * q;
+          }
         }
       }
     }
@@ -309,6 +407,152 @@ int xde_sde_noise(void* out, int64_t n, uint64_t seed, int64_t k, int mode, int 
   if (bits) XDE_LAUNCH((xde_sde_noise_kernel<float, true>), gr, b, st, prof, a);
   else if (dtype == XDE_F32) XDE_LAUNCH((xde_sde_noise_kernel<float, false>), gr, b, st, prof, a);
   else XDE_LAUNCH((xde_sde_noise_kernel<double, false>), gr, b, st, prof, a);
+  HIP_TRY(hipGetLastError());
+  return XDE_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// Milstein (derivative-free, Ito, diagonal noise): support point, step, and their backwards
+// ------------------------------------------------------------------------------------------
+namespace {
+
+// element alignment of every non-null operand; *vec = all of them 16-byte aligned
+int check_operands(const char* who, const void* const* ptrs, int count, size_t esz, bool* vec) {
+  *vec = true;
+  for (int i = 0; i < count; ++i) {
+    if (!ptrs[i]) continue;
+    if (!aligned_to(ptrs[i], esz)) return fail(XDE_EBADARG, std::string(who) + ": operand not aligned to its element type");
+    *vec = *vec && aligned16(ptrs[i]);
+  }
+  return XDE_OK;
+}
+
+template <typename T, bool VEC>
+void launch_support_backward(const SdeArgs& a, bool gf, bool gg, dim3 gr, dim3 b, hipStream_t st, ProfScope& prof) {
+  if (gf && gg) XDE_LAUNCH((xde_sde_em_backward_kernel<T, VEC, true, true, false>), gr, b, st, prof, a);
+  else if (gf) XDE_LAUNCH((xde_sde_em_backward_kernel<T, VEC, true, false, false>), gr, b, st, prof, a);
+  else XDE_LAUNCH((xde_sde_em_backward_kernel<T, VEC, false, true, false>), gr, b, st, prof, a);
+}
+
+template <typename T, bool VEC>
+void launch_milstein_backward(const SdeArgs& a, int mask, dim3 gr, dim3 b, hipStream_t st, ProfScope& prof) {
+  switch (mask) {  // bit 0: gf, bit 1: gg, bit 2: ggb
+    case 1: XDE_LAUNCH((xde_sde_milstein_backward_kernel<T, VEC, true, false, false>), gr, b, st, prof, a); break;
+    case 2: XDE_LAUNCH((xde_sde_milstein_backward_kernel<T, VEC, false, true, false>), gr, b, st, prof, a); break;
+    case 3: XDE_LAUNCH((xde_sde_milstein_backward_kernel<T, VEC, true, true, false>), gr, b, st, prof, a); break;
+    case 4: XDE_LAUNCH((xde_sde_milstein_backward_kernel<T, VEC, false, false, true>), gr, b, st, prof, a); break;
+    case 5: XDE_LAUNCH((xde_sde_milstein_backward_kernel<T, VEC, true, false, true>), gr, b, st, prof, a); break;
+    case 6: XDE_LAUNCH((xde_sde_milstein_backward_kernel<T, VEC, false, true, true>), gr, b, st, prof, a); break;
+    default: XDE_LAUNCH((xde_sde_milstein_backward_kernel<T, VEC, true, true, true>), gr, b, st, prof, a); break;
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int xde_sde_milstein_support(void* yb, const void* y0, const void* f, const void* g, int64_t n, double dt, double s, int dtype,
+                             void* stream) {
+  if (!yb || !y0 || !f || !g) return fail(XDE_EBADARG, "xde_sde_milstein_support: null pointer");
+  if (int rc = check_common("xde_sde_milstein_support", n, 0, dtype)) return rc;
+  const size_t esz = dtype == XDE_F32 ? 4 : 8;
+  const void* ptrs[4] = {yb, y0, f, g};
+  bool vec;
+  if (int rc = check_operands("xde_sde_milstein_support", ptrs, 4, esz, &vec)) return rc;
+  if (n == 0) return XDE_OK;
+  SdeArgs a = make_args(n, dtype == XDE_F32 ? 4 : 2, dt, s, 0, 0);
+  a.out0 = yb;
+  a.in0 = y0;
+  a.in1 = f;
+  a.in2 = g;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  ProfScope prof(XDE_KID_COMBINE, 4.0 * double(n) * double(esz));  // (a stage input: the stage combines' id)
+  const dim3 gr = grid_for(a.nblk), b(kBlock);
+  if (dtype == XDE_F32) {
+    if (vec) XDE_LAUNCH((xde_sde_em_step_kernel<float, true, false>), gr, b, st, prof, a);
+    else XDE_LAUNCH((xde_sde_em_step_kernel<float, false, false>), gr, b, st, prof, a);
+  } else {
+    if (vec) XDE_LAUNCH((xde_sde_em_step_kernel<double, true, false>), gr, b, st, prof, a);
+    else XDE_LAUNCH((xde_sde_em_step_kernel<double, false, false>), gr, b, st, prof, a);
+  }
+  HIP_TRY(hipGetLastError());
+  return XDE_OK;
+}
+
+int xde_sde_milstein_support_backward(void* gf, void* gg, const void* gyb, int64_t n, double dt, double s, int dtype, void* stream) {
+  if (!gyb) return fail(XDE_EBADARG, "xde_sde_milstein_support_backward: null pointer (gyb)");
+  if (int rc = check_common("xde_sde_milstein_support_backward", n, 0, dtype)) return rc;
+  const size_t esz = dtype == XDE_F32 ? 4 : 8;
+  const void* ptrs[3] = {gyb, gf, gg};
+  bool vec;
+  if (int rc = check_operands("xde_sde_milstein_support_backward", ptrs, 3, esz, &vec)) return rc;
+  if (n == 0 || (!gf && !gg)) return XDE_OK;
+  SdeArgs a = make_args(n, dtype == XDE_F32 ? 4 : 2, dt, s, 0, 0);
+  a.out0 = gf;
+  a.out1 = gg;
+  a.in0 = gyb;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  ProfScope prof(XDE_KID_COMBINE, double(1 + (gf ? 1 : 0) + (gg ? 1 : 0)) * double(n) * double(esz));
+  const dim3 gr = grid_for(a.nblk), b(kBlock);
+  if (dtype == XDE_F32) vec ? launch_support_backward<float, true>(a, gf, gg, gr, b, st, prof) : launch_support_backward<float, false>(a, gf, gg, gr, b, st, prof);
+  else vec ? launch_support_backward<double, true>(a, gf, gg, gr, b, st, prof) : launch_support_backward<double, false>(a, gf, gg, gr, b, st, prof);
+  HIP_TRY(hipGetLastError());
+  return XDE_OK;
+}
+
+int xde_sde_milstein_step(void* y1, const void* y0, const void* f, const void* g, const void* gb, int64_t n, double dt, double s,
+                          double c, uint64_t seed, int64_t k, int dtype, void* stream) {
+  if (!y1 || !y0 || !f || !g || !gb) return fail(XDE_EBADARG, "xde_sde_milstein_step: null pointer");
+  if (int rc = check_common("xde_sde_milstein_step", n, k, dtype)) return rc;
+  const size_t esz = dtype == XDE_F32 ? 4 : 8;
+  const void* ptrs[5] = {y1, y0, f, g, gb};
+  bool vec;
+  if (int rc = check_operands("xde_sde_milstein_step", ptrs, 5, esz, &vec)) return rc;
+  if (n == 0) return XDE_OK;
+  SdeArgs a = make_args(n, dtype == XDE_F32 ? 4 : 2, dt, s, seed, k);
+  a.c = c;
+  a.out0 = y1;
+  a.in0 = y0;
+  a.in1 = f;
+  a.in2 = g;
+  a.in3 = gb;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  ProfScope prof(XDE_KID_COMBINE_FUSE, 5.0 * double(n) * double(esz));  // (the SDE's fuse, as the EM step)
+  const dim3 gr = grid_for(a.nblk), b(kBlock);
+  if (dtype == XDE_F32) {
+    if (vec) XDE_LAUNCH((xde_sde_milstein_step_kernel<float, true>), gr, b, st, prof, a);
+    else XDE_LAUNCH((xde_sde_milstein_step_kernel<float, false>), gr, b, st, prof, a);
+  } else {
+    if (vec) XDE_LAUNCH((xde_sde_milstein_step_kernel<double, true>), gr, b, st, prof, a);
+    else XDE_LAUNCH((xde_sde_milstein_step_kernel<double, false>), gr, b, st, prof, a);
+  }
+  HIP_TRY(hipGetLastError());
+  return XDE_OK;
+}
+
+int xde_sde_milstein_backward(void* gf, void* gg, void* ggb, const void* gy1, int64_t n, double dt, double s, double c, uint64_t seed,
+                              int64_t k, int dtype, void* stream) {
+  if (!gy1) return fail(XDE_EBADARG, "xde_sde_milstein_backward: null pointer (gy1)");
+  if (int rc = check_common("xde_sde_milstein_backward", n, k, dtype)) return rc;
+  const size_t esz = dtype == XDE_F32 ? 4 : 8;
+  const void* ptrs[4] = {gy1, gf, gg, ggb};
+  bool vec;
+  if (int rc = check_operands("xde_sde_milstein_backward", ptrs, 4, esz, &vec)) return rc;
+  const int mask = (gf ? 1 : 0) | (gg ? 2 : 0) | (ggb ? 4 : 0);
+  if (n == 0 || !mask) return XDE_OK;
+  SdeArgs a = make_args(n, dtype == XDE_F32 ? 4 : 2, dt, s, seed, k);
+  a.c = c;
+  a.out0 = gf;
+  a.out1 = gg;
+  a.out2 = ggb;
+  a.in0 = gy1;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  ProfScope prof(XDE_KID_COMBINE, double(1 + (gf ? 1 : 0) + (gg ? 1 : 0) + (ggb ? 1 : 0)) * double(n) * double(esz));
+  const dim3 gr = grid_for(a.nblk), b(kBlock);
+  if (dtype == XDE_F32) vec ? launch_milstein_backward<float, true>(a, mask, gr, b, st, prof) : launch_milstein_backward<float, false>(a, mask, gr, b, st, prof);
+  else vec ? launch_milstein_backward<double, true>(a, mask, gr, b, st, prof) : launch_milstein_backward<double, false>(a, mask, gr, b, st, prof);
   HIP_TRY(hipGetLastError());
   return XDE_OK;
 }

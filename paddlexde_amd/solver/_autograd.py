@@ -1,4 +1,4 @@
-"""Autograd nodes around the step kernels (xde_stage_combine, xde_interp_rows, xde_sde_em_step) for discretise-then-optimise training.
+"""Autograd nodes around the step kernels (xde_stage_combine, xde_interp_rows, xde_sde_em_step, xde_sde_milstein_step) for discretise-then-optimise training.
 
 The reference trains by back-propagating through its eager solver ops (example/ode_demo.py:51-53:
 ``pred_y = odeint(func, batch_y0, t_span, solver=RK4); loss.backward()``).  Here the forward is one combine launch
@@ -121,3 +121,57 @@ class SdeEulerFn(torch.autograd.Function):
             dt, s, seed, k = ctx.meta
             ctx.backend._sde_em_backward(gf, gg, g, dt, s, seed, k)
         return (None, None, None, None, None, g if need_y0 else None, gf, gg)
+
+
+def _cotangent(g):
+    g = g.contiguous()
+    return g.clone() if g.data_ptr() % 16 else g
+
+
+class SdeSupportFn(torch.autograd.Function):
+    """Milstein's support point ``yb = (y0 + f*dt) + g*s`` (``HipBackend._sde_milstein_support``) as an autograd node: backward is one
+    launch writing ``gf = gyb*dt`` and ``gg = gyb*s`` (xde_sde_milstein_support_backward); ``gy0 = gyb`` needs no launch."""
+
+    @staticmethod
+    def forward(ctx, backend, dt, s, y0, f, g):
+        out = torch.empty_like(y0)
+        backend._sde_milstein_support(out, y0.detach(), f.detach(), g.detach(), dt, s)
+        ctx.backend, ctx.meta = backend, (float(dt), float(s))
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        need_y0, need_f, need_g = ctx.needs_input_grad[3:6]
+        g = _cotangent(g)
+        gf = torch.empty_like(g) if need_f else None
+        gg = torch.empty_like(g) if need_g else None
+        if gf is not None or gg is not None:
+            ctx.backend._sde_milstein_support_backward(gf, gg, g, *ctx.meta)
+        return (None, None, None, g if need_y0 else None, gf, gg)
+
+
+class SdeMilsteinFn(torch.autograd.Function):
+    """One Milstein step ``y1 = ((y0 + f*dt) + g*w) + (gb - g)*q``, ``w = s*Z``, ``q = c*(w*w - |dt|)``
+    (``HipBackend._sde_milstein_step``) as an autograd node.  The node keeps only ``(dt, s, c, seed, k)``: backward regenerates Z from
+    the same counter in the launch that writes ``gf = gy1*dt``, ``gg = gy1*(w - q)`` and ``ggb = gy1*q`` (xde_sde_milstein_backward);
+    ``gy0 = gy1`` needs no launch."""
+
+    @staticmethod
+    def forward(ctx, backend, dt, s, c, seed, k, y0, f, g, gb):
+        out = torch.empty_like(y0)
+        backend._sde_milstein_step(out, y0.detach(), f.detach(), g.detach(), gb.detach(), dt, s, c, seed, k)
+        ctx.backend, ctx.meta = backend, (float(dt), float(s), float(c), int(seed), int(k))
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        need_y0, need_f, need_g, need_gb = ctx.needs_input_grad[6:10]
+        g = _cotangent(g)
+        gf = torch.empty_like(g) if need_f else None
+        gg = torch.empty_like(g) if need_g else None
+        ggb = torch.empty_like(g) if need_gb else None
+        if gf is not None or gg is not None or ggb is not None:
+            ctx.backend._sde_milstein_backward(gf, gg, ggb, g, *ctx.meta)
+        return (None, None, None, None, None, None, g if need_y0 else None, gf, gg, ggb)

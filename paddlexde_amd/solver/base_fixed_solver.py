@@ -21,7 +21,7 @@ from ..xde.base_dde import DDE_DAMPING, BaseDDE
 from ..xde.base_ode import BaseODE
 from ..xde.base_sde import BaseSDE
 from ..xde.base_xde import BaseXDE
-from ._autograd import CombineFn, InterpRowsFn, SdeEulerFn
+from ._autograd import CombineFn, InterpRowsFn, SdeEulerFn, SdeMilsteinFn, SdeSupportFn
 from ._common import as_operand, np_dtype, storage_ptr, t_span_to_host, upload
 
 _one_third = 1 / 3
@@ -114,7 +114,7 @@ class _SubSteps:
 class FixedSolver(metaclass=abc.ABCMeta):
     order: int
 
-    steps_sde = False  # the step is a convergent scheme for Ito SDEs (a BaseSDE problem): Euler, as Euler-Maruyama
+    steps_sde = False  # the step is a convergent scheme for Ito SDEs (a BaseSDE problem): Euler, as Euler-Maruyama, and Milstein
 
     graphable = True  # the step's control flow does not depend on data (False: AdamsBashforthMoulton)
     GRAPH_MIN_STEPS = 4
@@ -165,13 +165,13 @@ class FixedSolver(metaclass=abc.ABCMeta):
             raise NotImplementedError("pipeline='graph' replays a captured step and cannot call xde.on_integrate_step_end; "
                                       "use pipeline='sync' (or the default 'auto', which then keeps the eager loop)")
         # the wrapper's fuse is what xde_stage_combine computes: BaseODE's `dy*dt + y0` or BaseDDE's damped form; BaseSDE's
-        # Euler-Maruyama update is xde_sde_em_step
+        # Euler-Maruyama update is xde_sde_em_step (Milstein adds its correction to it: xde_sde_milstein_step)
         fuse_impl = getattr(type(xde), "fuse", None)
         self._sde = fuse_impl is BaseSDE.fuse
         if self._sde:
             if not self.steps_sde:
                 raise NotImplementedError("{} does not step SDEs: its tableau does not converge for Ito SDEs; use Euler "
-                                          "(Euler-Maruyama)".format(type(self).__name__))
+                                          "(Euler-Maruyama) or Milstein".format(type(self).__name__))
             if pipeline == "graph":
                 raise NotImplementedError("pipeline='graph' replays one captured step, which cannot advance the SDE's grid-step "
                                           "counter; use pipeline='sync' (or the default 'auto', which keeps the eager loop for SDEs)")
@@ -251,6 +251,33 @@ class FixedSolver(metaclass=abc.ABCMeta):
             return SdeEulerFn.apply(self.backend, float(dt), float(s), self.xde.seed, k, y0, f, g), f
         out = self._y1_out if self._y1_out is not None else torch.empty_like(y0)
         self.backend._sde_em_step(out, y0, f, g, float(dt), float(s), self.xde.seed, k)
+        return out, f
+
+    def _milstein_step(self, t0, dtt, y0, dt):
+        """One derivative-free Milstein step of a BaseSDE (Kloeden & Platen's explicit strong order 1.0 scheme, Ito, diagonal noise):
+        the support point ``yb = (y0 + f*dt) + g*s`` (one launch), ``gb = diffusion(t0, yb)``, and
+        ``y1 = ((y0 + f*dt) + g*w) + (gb - g)*q`` with ``w = s*Z``, ``q = c*(w*w - |dt|)`` (one xde_sde_milstein_step launch) —
+        ``s = sqrt(|dt|)`` and ``c = 0.5/sqrt(|dt|)`` computed in float64 and rounded to the state dtype, ``c = 0`` for a zero-length
+        step (which then returns y0), Z the normals of (xde.seed, grid step k) as in ``_em_step``.  Through SdeSupportFn /
+        SdeMilsteinFn when an operand is differentiated.  ``nfe`` counts steps, as Euler's does: one per step, which here stands for
+        one drift and two diffusion evaluations.  Returns ``(y1, f)``."""
+        self.nfe += 1
+        f, g = self.move(t0, dtt, y0)
+        f, g = as_operand(f, like=y0), as_operand(g, like=y0)
+        T = np_dtype(y0.dtype)
+        root = np.sqrt(abs(np.float64(dt)))
+        s = T(root)
+        c = T(0.5 / root) if root > 0 else T(0.0)
+        k = self._k if self._k is not None else 0  # (a step() call outside integrate() is the first step of a walk)
+        if torch.is_grad_enabled() and (y0.requires_grad or f.requires_grad or g.requires_grad):
+            yb = SdeSupportFn.apply(self.backend, float(dt), float(s), y0, f, g)
+            gb = as_operand(self.xde.diffusion(t0, yb), like=y0)
+            return SdeMilsteinFn.apply(self.backend, float(dt), float(s), float(c), self.xde.seed, k, y0, f, g, gb), f
+        yb = torch.empty_like(y0)
+        self.backend._sde_milstein_support(yb, y0, f, g, float(dt), float(s))
+        gb = as_operand(self.xde.diffusion(t0, yb), like=y0)
+        out = self._y1_out if self._y1_out is not None else torch.empty_like(y0)
+        self.backend._sde_milstein_step(out, y0, f, g, gb, float(dt), float(s), float(c), self.xde.seed, k)
         return out, f
 
     def _combine_pre(self, y0, pre, ks, coef, dt, scale, out=None):

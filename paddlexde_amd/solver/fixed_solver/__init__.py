@@ -1,7 +1,8 @@
 """Fixed-grid solver classes (the names the reference exports from this package)."""
-from . import adams, euler, midpoint, rk4
+from . import adams, euler, midpoint, milstein, rk4
 
 RK4, Euler, Midpoint = rk4.RK4, euler.Euler, midpoint.Midpoint
 AdamsBashforthMoulton = adams.AdamsBashforthMoulton
+Milstein = milstein.Milstein
 
-__all__ = ["AdamsBashforthMoulton", "Euler", "Midpoint", "RK4"]
+__all__ = ["AdamsBashforthMoulton", "Euler", "Midpoint", "Milstein", "RK4"]

@@ -4,7 +4,7 @@
 and dtype that multiplies the Brownian increment element by element.  ``move`` evaluates both coefficients and ``fuse`` is the Ito
 Euler-Maruyama update ``(y0 + f*dt) + g*dW``, the step the reference meant (its ``move`` computes ``f(t0, y0)`` and
 ``g(t0, y0) * I_k`` with ``I_k = bm(t0, t1)``; its ``fuse`` is marked TODO).  The fixed-step solvers never call ``fuse``: they map a
-``BaseSDE`` onto xde_sde_em_step, which forms ``dW = sqrt(|dt|) * Z`` from a counter-based generator inside the kernel (no Brownian
+``BaseSDE`` onto xde_sde_em_step (Euler) or xde_sde_milstein_step (Milstein), which form ``dW = sqrt(|dt|) * Z`` from a counter-based generator inside the kernel (no Brownian
 object: the noise of element e at grid step k is a function of (seed, k, e) — include/xde_hip_sde.h).
 """
 import numpy as np
@@ -47,15 +47,18 @@ class BaseSDE(BaseXDE):
     def handle(self, h, ts):
         pass
 
-    def move(self, t0, dt, y0):
-        """base_sde.py:43-58 — the drift and the diffusion at (t0, y0); the solver draws the increment."""
-        f = self.f(t0, y0)
-        g = self.g(t0, y0)
-        if not torch.is_tensor(g) or g.shape != y0.shape or g.dtype != y0.dtype:
+    def diffusion(self, t, y):
+        """``g(t, y)``, checked: a tensor of y's shape and dtype (diagonal noise).  Milstein's support evaluation calls it too."""
+        g = self.g(t, y)
+        if not torch.is_tensor(g) or g.shape != y.shape or g.dtype != y.dtype:
             got = "{} {}".format(tuple(g.shape), g.dtype) if torch.is_tensor(g) else type(g).__name__
             raise ValueError("the diffusion g(t, y) must return a tensor of y's shape {} and dtype {} (diagonal noise), got {}".format(
-                tuple(y0.shape), y0.dtype, got))
-        return f, g
+                tuple(y.shape), y.dtype, got))
+        return g
+
+    def move(self, t0, dt, y0):
+        """base_sde.py:43-58 — the drift and the diffusion at (t0, y0); the solver draws the increment."""
+        return self.f(t0, y0), self.diffusion(t0, y0)
 
     def fuse(self, dy, dt, y0):
         """Euler-Maruyama: ``dy = (f, g, dW)`` -> ``(y0 + f*dt) + g*dW`` (the kernel's op order, with ``dW = s*Z``)."""
