@@ -784,61 +784,42 @@ class HipBackend:
     # -- sdeint's Euler-Maruyama and Milstein steps (include/xde_hip_sde.h) ---------------------------------------------------------------
     # Private for the reason _interp_rows is: the public methods are the contract tests/_cpu_double.py mirrors.  Only the fixed-step
     # solvers' SDE path (and its autograd node) call these.
-    @staticmethod
-    def _sde_operands(who, *ts):
-        like = ts[0]
-        for x in ts:
+    def _sde_call(self, who, outs, ins, *scalars):
+        """One launch of the step entry point ``xde<who>(*outs, *ins, n, *scalars, dtype, stream)``: contiguous tensors of one shape and
+        dtype on the device; an output given as None goes in as a null pointer (a skipped output of a backward)."""
+        self._require_device(*outs, *ins)
+        like = ins[0]
+        for x in (*ins, *outs):
             if x is not None and (not x.is_contiguous() or x.shape != like.shape or x.dtype != like.dtype):
                 raise XdeError("{}: the operands must be contiguous tensors of one shape and dtype".format(who))
+        rc = getattr(self.lib, "xde" + who)(*[_ptr(x) for x in (*outs, *ins)], like.numel(), *scalars, dtype_code(like.dtype),
+                                            self._stream(like))
+        self._check(rc, "xde" + who)
 
     def _sde_em_step(self, y1, y0, f, g, dt, s, seed, k):
         """``y1 = (y0 + f*dt) + g*(s*Z)`` with Z the normals of (``seed``, step ``k``); ``y1`` may be ``y0``.  One launch."""
-        self._require_device(y1, y0, f, g)
-        self._sde_operands("_sde_em_step", y1, y0, f, g)
-        rc = self.lib.xde_sde_em_step(y1.data_ptr(), y0.data_ptr(), f.data_ptr(), g.data_ptr(), y0.numel(), float(dt), float(s),
-                                      int(seed), int(k), dtype_code(y0.dtype), self._stream(y0))
-        self._check(rc, "xde_sde_em_step")
+        self._sde_call("_sde_em_step", (y1,), (y0, f, g), float(dt), float(s), int(seed), int(k))
 
     def _sde_em_backward(self, gf, gg, gy1, dt, s, seed, k):
         """``gf = gy1*dt`` and ``gg = gy1*(s*Z)`` (either may be None: skipped), one launch regenerating the forward's Z."""
-        self._require_device(gf, gg, gy1)
-        self._sde_operands("_sde_em_backward", gy1, gf, gg)
-        rc = self.lib.xde_sde_em_backward(_ptr(gf), _ptr(gg), gy1.data_ptr(), gy1.numel(), float(dt), float(s), int(seed), int(k),
-                                          dtype_code(gy1.dtype), self._stream(gy1))
-        self._check(rc, "xde_sde_em_backward")
+        self._sde_call("_sde_em_backward", (gf, gg), (gy1,), float(dt), float(s), int(seed), int(k))
 
     def _sde_milstein_support(self, yb, y0, f, g, dt, s):
         """Milstein's support point ``yb = (y0 + f*dt) + g*s``.  One launch, no generator."""
-        self._require_device(yb, y0, f, g)
-        self._sde_operands("_sde_milstein_support", yb, y0, f, g)
-        rc = self.lib.xde_sde_milstein_support(yb.data_ptr(), y0.data_ptr(), f.data_ptr(), g.data_ptr(), y0.numel(), float(dt), float(s),
-                                               dtype_code(y0.dtype), self._stream(y0))
-        self._check(rc, "xde_sde_milstein_support")
+        self._sde_call("_sde_milstein_support", (yb,), (y0, f, g), float(dt), float(s))
 
     def _sde_milstein_support_backward(self, gf, gg, gyb, dt, s):
         """``gf = gyb*dt`` and ``gg = gyb*s`` (either may be None: skipped), one launch."""
-        self._require_device(gf, gg, gyb)
-        self._sde_operands("_sde_milstein_support_backward", gyb, gf, gg)
-        rc = self.lib.xde_sde_milstein_support_backward(_ptr(gf), _ptr(gg), gyb.data_ptr(), gyb.numel(), float(dt), float(s),
-                                                        dtype_code(gyb.dtype), self._stream(gyb))
-        self._check(rc, "xde_sde_milstein_support_backward")
+        self._sde_call("_sde_milstein_support_backward", (gf, gg), (gyb,), float(dt), float(s))
 
     def _sde_milstein_step(self, y1, y0, f, g, gb, dt, s, c, seed, k):
         """``y1 = ((y0 + f*dt) + g*w) + (gb - g)*q`` with ``w = s*Z``, ``q = c*(w*w - |dt|)`` and Z the normals of (``seed``, step
         ``k``); ``y1`` may be ``y0``.  One launch."""
-        self._require_device(y1, y0, f, g, gb)
-        self._sde_operands("_sde_milstein_step", y1, y0, f, g, gb)
-        rc = self.lib.xde_sde_milstein_step(y1.data_ptr(), y0.data_ptr(), f.data_ptr(), g.data_ptr(), gb.data_ptr(), y0.numel(), float(dt),
-                                            float(s), float(c), int(seed), int(k), dtype_code(y0.dtype), self._stream(y0))
-        self._check(rc, "xde_sde_milstein_step")
+        self._sde_call("_sde_milstein_step", (y1,), (y0, f, g, gb), float(dt), float(s), float(c), int(seed), int(k))
 
     def _sde_milstein_backward(self, gf, gg, ggb, gy1, dt, s, c, seed, k):
         """``gf = gy1*dt``, ``gg = gy1*(w - q)`` and ``ggb = gy1*q`` (any may be None: skipped), one launch regenerating the forward's Z."""
-        self._require_device(gf, gg, ggb, gy1)
-        self._sde_operands("_sde_milstein_backward", gy1, gf, gg, ggb)
-        rc = self.lib.xde_sde_milstein_backward(_ptr(gf), _ptr(gg), _ptr(ggb), gy1.data_ptr(), gy1.numel(), float(dt), float(s), float(c),
-                                                int(seed), int(k), dtype_code(gy1.dtype), self._stream(gy1))
-        self._check(rc, "xde_sde_milstein_backward")
+        self._sde_call("_sde_milstein_backward", (gf, gg, ggb), (gy1,), float(dt), float(s), float(c), int(seed), int(k))
 
     def _sde_noise(self, out, seed, k, bits=False):
         """The generator's output for (``seed``, step ``k``) into the contiguous ``out``: the normals Z (``out``'s dtype), or with

@@ -3,9 +3,15 @@
 //
 // One lane serves one Philox4x32-10 call: 4 fp32 or 2 fp64 elements, i.e. exactly one 16-byte vector of every operand.  The
 // EM forward reads y0, f, g once and writes y1 once (4 n elt bytes), the Milstein forward reads gb as well (5 n); the noise lives in
-// registers only, and the backward regenerates it from the same counter instead of reading it back.  The Milstein support point is the
-// EM kernels with the generator compiled out (NOISE = false: s in the place of s * Z).  A lane whose block runs past n (the tail), or any launch whose pointers are not
-// all 16-byte aligned, takes the scalar path with the same bits.  Grid-stride loop over at most grid_cap() workgroups of kBlock.
+// registers only, and the backward regenerates it from the same counter instead of reading it back.
+//
+// The file is three layers.  Each formula is written once, as a per-element functor (EmStep, EmBackward, MilsteinStep,
+// MilsteinBackward); the Milstein support point is the EM functors with NOISE = false (s in the place of s * Z, the generator compiled
+// out).  One kernel, xde_sde_step_kernel, owns the lane loop for all of them: a lane whose block runs past n (the tail), or any launch
+// whose pointers are not all 16-byte aligned, takes the scalar path with the same bits; grid-stride over at most grid_cap() workgroups
+// of kBlock.  One host launcher, sde_launch, owns the argument checks, the profiling scope and the dtype x alignment x output-mask
+// dispatch; the entry points only name their operands.  xde_sde_noise, the generator alone, keeps a kernel and a host body of its own:
+// it is what the tests read Z back with, an independent statement of which counter serves which element.
 // Built with -ffp-contract=off like the rest of the library; the math functions are the precise ones (no fast-math, no __sinf).
 
 #include "xde_common.hpp"
@@ -79,183 +85,120 @@ __device__ __forceinline__ void normals(uint64_t j, uint32_t k, uint32_t key0, u
 }
 
 struct SdeArgs {
-  void* out0;       // y1 | gf | out
-  void* out1;       // gg
-  void* out2;       // ggb
-  const void* in0;  // y0 | gy1
-  const void* in1;  // f
-  const void* in2;  // g
-  const void* in3;  // gb
-  int64_t n;        // elements (bits mode: words)
-  int64_t nblk;     // Philox calls = lanes of work
+  void* out[3];       // y1 | gf, gg, ggb | the noise kernel's output
+  const void* in[4];  // y0, f, g, gb | gy1
+  int64_t n;          // elements (bits mode: words)
+  int64_t nblk;       // Philox calls = lanes of work
   double dt, s, c;
   uint32_t key0, key1, k;
 };
 
-// NOISE = false is the Milstein support point yb = (y0 + f * dt) + g * s: no generator, the same loads and stores
-template <typename T, bool VEC, bool NOISE = true>
-__global__ __launch_bounds__(kBlock) void xde_sde_em_step_kernel(SdeArgs a) {
-  constexpr int W = Block<T>::W;
+// the step's scalars in the state dtype; ad = |dt|
+template <typename T> struct Coef {
+  T dt, s, c, ad;
+};
+
+// The formulas, one element each: (inputs x, the element's Z, the scalars) -> outputs o, in the written op order.  NI inputs, NO
+// outputs, and ZMASK = the outputs that depend on Z (bit i: output i).  NOISE = false puts s in the place of s * Z.
+struct EmStep {  // y1 = (y0 + f * dt) + g * (s * Z)        x = y0, f, g
+  static constexpr int NI = 3, NO = 1, ZMASK = 1;
+  template <bool NOISE, typename T> __device__ static void apply(const T (&x)[NI], T z, const Coef<T>& k, T (&o)[NO]) {
+    o[0] = (x[0] + x[1] * k.dt) + x[2] * (NOISE ? k.s * z : k.s);
+  }
+};
+
+struct EmBackward {  // gf = gy1 * dt, gg = gy1 * (s * Z)     x = gy1
+  static constexpr int NI = 1, NO = 2, ZMASK = 2;
+  template <bool NOISE, typename T> __device__ static void apply(const T (&x)[NI], T z, const Coef<T>& k, T (&o)[NO]) {
+    o[0] = x[0] * k.dt;
+    o[1] = x[0] * (NOISE ? k.s * z : k.s);
+  }
+};
+
+struct MilsteinStep {  // w = s * Z, q = c * (w * w - |dt|), y1 = ((y0 + f * dt) + g * w) + (gb - g) * q        x = y0, f, g, gb
+  static constexpr int NI = 4, NO = 1, ZMASK = 1;
+  template <bool NOISE, typename T> __device__ static void apply(const T (&x)[NI], T z, const Coef<T>& k, T (&o)[NO]) {
+    static_assert(NOISE, "Milstein has no noise-free form");
+    const T w = k.s * z, q = k.c * (w * w - k.ad);
+    o[0] = ((x[0] + x[1] * k.dt) + x[2] * w) + (x[3] - x[2]) * q;
+  }
+};
+
+struct MilsteinBackward {  // gf = gy1 * dt, gg = gy1 * (w - q), ggb = gy1 * q     x = gy1
+  static constexpr int NI = 1, NO = 3, ZMASK = 6;
+  template <bool NOISE, typename T> __device__ static void apply(const T (&x)[NI], T z, const Coef<T>& k, T (&o)[NO]) {
+    static_assert(NOISE, "Milstein has no noise-free form");
+    const T w = k.s * z, q = k.c * (w * w - k.ad);
+    o[0] = x[0] * k.dt;
+    o[1] = x[0] * (w - q);
+    o[2] = x[0] * q;
+  }
+};
+
+// one lane's vector of the outputs in M: formula on the loaded packs, 16-byte stores
+template <typename T, bool NOISE, class Op, int M>
+__device__ __forceinline__ void store_packs(const Pack<T, true> (&X)[Op::NI], const T (&z)[Block<T>::W], const Coef<T>& k,
+                                            T* const (&out)[Op::NO], int64_t j) {
+  if (!M) return;
+  Pack<T, true> O[Op::NO];
+#pragma unroll
+  for (int v = 0; v < Block<T>::W; ++v) {
+    T x[Op::NI], o[Op::NO];
+#pragma unroll
+    for (int i = 0; i < Op::NI; ++i) x[i] = X[i].v[v];
+    Op::template apply<NOISE>(x, z[v], k, o);
+#pragma unroll
+    for (int i = 0; i < Op::NO; ++i) O[i].v[v] = o[i];
+  }
+#pragma unroll
+  for (int i = 0; i < Op::NO; ++i)
+    if (M >> i & 1) O[i].store(out[i], j);
+}
+
+// The lane loop of every step kernel.  MASK = the outputs to write (bit i: a.out[i]); the others may be null and are never touched: their
+// stores, and the generator when no written output depends on Z, are compiled out.  A lane loads all its operands before the generator
+// runs (vector path) and before it stores anything, so an output may alias an input; the outputs that do not depend on Z are stored
+// ahead of the generator.
+template <typename T, bool VEC, bool NOISE, class Op, int MASK>
+__global__ __launch_bounds__(kBlock) void xde_sde_step_kernel(SdeArgs a) {
+  constexpr int W = Block<T>::W, NI = Op::NI, NO = Op::NO;
+  constexpr bool Z = NOISE && (MASK & Op::ZMASK) != 0;
+  constexpr int EARLY = Z ? (MASK & ~Op::ZMASK) : 0;
   using P = Pack<T, true>;
   static_assert(P::W == W, "one Philox call per 16-byte vector");
-  const T dt = T(a.dt), s = T(a.s);
-  T* y1 = static_cast<T*>(a.out0);
-  const T* y0 = static_cast<const T*>(a.in0);
-  const T* f = static_cast<const T*>(a.in1);
-  const T* g = static_cast<const T*>(a.in2);
+  const int64_t n = a.n, nblk = a.nblk;  // (the scalars are read at entry, in one fetch with dt and s; the pointers where the loop uses them)
+  const T dt = T(a.dt);
+  const Coef<T> k{dt, T(a.s), T(a.c), abs_(dt)};
   const int64_t stride = int64_t(gridDim.x) * kBlock;
-  for (int64_t j = int64_t(blockIdx.x) * kBlock + threadIdx.x; j < a.nblk; j += stride) {
+  for (int64_t j = int64_t(blockIdx.x) * kBlock + threadIdx.x; j < nblk; j += stride) {
     const int64_t e0 = j * W;
-    if (VEC && e0 + W <= a.n) {
-      const P Y = P::load(y0, j), F = P::load(f, j), G = P::load(g, j);  // (issued before the generator runs)
-      T z[W];
-      if (NOISE) normals(uint64_t(j), a.k, a.key0, a.key1, z);
-      P o;
+    T z[W] = {};
+    const T* in[NI];
+    T* out[NO];
 #pragma unroll
-      for (int v = 0; v < W; ++v) o.v[v] = (Y.v[v] + F.v[v] * dt) + G.v[v] * (NOISE ? s * z[v] : s);
-      o.store(y1, j);
+    for (int i = 0; i < NI; ++i) in[i] = static_cast<const T*>(a.in[i]);
+#pragma unroll
+    for (int i = 0; i < NO; ++i) out[i] = static_cast<T*>(a.out[i]);
+    if (VEC && e0 + W <= n) {
+      P X[NI];
+#pragma unroll
+      for (int i = 0; i < NI; ++i) X[i] = P::load(in[i], j);
+      store_packs<T, NOISE, Op, EARLY>(X, z, k, out, j);
+      if (Z) normals(uint64_t(j), a.k, a.key0, a.key1, z);
+      store_packs<T, NOISE, Op, MASK & ~EARLY>(X, z, k, out, j);
     } else {
-      T z[W];
-      if (NOISE) normals(uint64_t(j), a.k, a.key0, a.key1, z);
+      if (Z) normals(uint64_t(j), a.k, a.key0, a.key1, z);
 #pragma unroll
       for (int v = 0; v < W; ++v) {
         const int64_t e = e0 + v;
-        if (e < a.n) y1[e] = (y0[e] + f[e] * dt) + g[e] * (NOISE ? s * z[v] : s);
-      }
-    }
-  }
-}
-
-template <typename T, bool VEC, bool GF, bool GG, bool NOISE = true>
-__global__ __launch_bounds__(kBlock) void xde_sde_em_backward_kernel(SdeArgs a) {
-  constexpr int W = Block<T>::W;
-  using P = Pack<T, true>;
-  const T dt = T(a.dt), s = T(a.s);
-  T* gf = static_cast<T*>(a.out0);
-  T* gg = static_cast<T*>(a.out1);
-  const T* gy = static_cast<const T*>(a.in0);
-  const int64_t stride = int64_t(gridDim.x) * kBlock;
-  for (int64_t j = int64_t(blockIdx.x) * kBlock + threadIdx.x; j < a.nblk; j += stride) {
-    const int64_t e0 = j * W;
-    if (VEC && e0 + W <= a.n) {
-      const P Y = P::load(gy, j);
-      if (GF) {
-        P o;
+        if (e < n) {
+          T x[NI], o[NO];
 #pragma unroll
-        for (int v = 0; v < W; ++v) o.v[v] = Y.v[v] * dt;
-        o.store(gf, j);
-      }
-      if (GG) {
-        T z[W];
-        if (NOISE) normals(uint64_t(j), a.k, a.key0, a.key1, z);
-        P o;
+          for (int i = 0; i < NI; ++i) x[i] = in[i][e];
+          Op::template apply<NOISE>(x, z[v], k, o);
 #pragma unroll
-        for (int v = 0; v < W; ++v) o.v[v] = Y.v[v] * (NOISE ? s * z[v] : s);
-        o.store(gg, j);
-      }
-    } else {
-      T z[W];
-      if (GG && NOISE) normals(uint64_t(j), a.k, a.key0, a.key1, z);
-#pragma unroll
-      for (int v = 0; v < W; ++v) {
-        const int64_t e = e0 + v;
-        if (e < a.n) {
-          if (GF) gf[e] = gy[e] * dt;
-          if (GG) gg[e] = gy[e] * (NOISE ? s * z[v] : s);
-        }
-      }
-    }
-  }
-}
-
-// w = s * Z, q = c * (w * w - |dt|), y1 = ((y0 + f * dt) + g * w) + (gb - g) * q
-template <typename T, bool VEC>
-__global__ __launch_bounds__(kBlock) void xde_sde_milstein_step_kernel(SdeArgs a) {
-  constexpr int W = Block<T>::W;
-  using P = Pack<T, true>;
-  const T dt = T(a.dt), s = T(a.s), c = T(a.c), ad = abs_(dt);
-  T* y1 = static_cast<T*>(a.out0);
-  const T* y0 = static_cast<const T*>(a.in0);
-  const T* f = static_cast<const T*>(a.in1);
-  const T* g = static_cast<const T*>(a.in2);
-  const T* gb = static_cast<const T*>(a.in3);
-  const int64_t stride = int64_t(gridDim.x) * kBlock;
-  for (int64_t j = int64_t(blockIdx.x) * kBlock + threadIdx.x; j < a.nblk; j += stride) {
-    const int64_t e0 = j * W;
-    if (VEC && e0 + W <= a.n) {
-      const P Y = P::load(y0, j), F = P::load(f, j), G = P::load(g, j), GB = P::load(gb, j);  // (issued before the generator runs)
-      T z[W];
-      normals(uint64_t(j), a.k, a.key0, a.key1, z);
-      P o;
-#pragma unroll
-      for (int v = 0; v < W; ++v) {
-        const T w = s * z[v], q = c * (w * w - ad);
-        o.v[v] = ((Y.v[v] + F.v[v] * dt) + G.v[v] * w) + (GB.v[v] - G.v[v]) * q;
-      }
-      o.store(y1, j);
-    } else {
-      T z[W];
-      normals(uint64_t(j), a.k, a.key0, a.key1, z);
-#pragma unroll
-      for (int v = 0; v < W; ++v) {
-        const int64_t e = e0 + v;
-        if (e < a.n) {
-          const T w = s * z[v], q = c * (w * w - ad);
-          y1[e] = ((y0[e] + f[e] * dt) + g[e] * w) + (gb[e] - g[e]) * q;
-        }
-      }
-    }
-  }
-}
-
-// gf = gy1 * dt, gg = gy1 * (w - q), ggb = gy1 * q
-template <typename T, bool VEC, bool GF, bool GG, bool GGB>
-__global__ __launch_bounds__(kBlock) void xde_sde_milstein_backward_kernel(SdeArgs a) {
-  constexpr int W = Block<T>::W;
-  using P = Pack<T, true>;
-  const T dt = T(a.dt), s = T(a.s), c = T(a.c), ad = abs_(dt);
-  T* gf = static_cast<T*>(a.out0);
-  T* gg = static_cast<T*>(a.out1);
-  T* ggb = static_cast<T*>(a.out2);
-  const T* gy = static_cast<const T*>(a.in0);
-  const int64_t stride = int64_t(gridDim.x) * kBlock;
-  for (int64_t j = int64_t(blockIdx.x) * kBlock + threadIdx.x; j < a.nblk; j += stride) {
-    const int64_t e0 = j * W;
-    if (VEC && e0 + W <= a.n) {
-      const P Y = P::load(gy, j);
-      if (GF) {
-        P o;
-#pragma unroll
-        for (int v = 0; v < W; ++v) o.v[v] = Y.v[v] * dt;
-        o.store(gf, j);
-      }
-      if (GG || GGB) {
-        T z[W];
-        normals(uint64_t(j), a.k, a.key0, a.key1, z);
-        P og, ob;
-#pragma unroll
-        for (int v = 0; v < W; ++v) {
-          const T w = s * z[v], q = c * (w * w - ad);
-          og.v[v] = Y.v[v] * (w - q);
-          ob.v[v] = Y.v[v] * q;
-        }
-        if (GG) og.store(gg, j);
-        if (GGB) ob.store(ggb, j);
-      }
-    } else {
-      T z[W];
-      if (GG || GGB) normals(uint64_t(j), a.k, a.key0, a.key1, z);
-#pragma unroll
-      for (int v = 0; v < W; ++v) {
-        const int64_t e = e0 + v;
-        if (e < a.n) {
-          const T y = gy[e];
-          if (GF) gf[e] = y * dt;
-          if (GG || GGB) {
-            const T w = s * z[v], q = c * (w * w - ad);
-            if (GG) gg[e] = y * (w - q);
-            if (GGB) ggb[e] = y * q;
-          }
+          for (int i = 0; i < NO; ++i)
+            if (MASK >> i & 1) out[i][e] = o[i];
         }
       }
     }
@@ -270,14 +213,14 @@ __global__ __launch_bounds__(kBlock) void xde_sde_noise_kernel(SdeArgs a) {
     const int64_t e0 = j * W;
     if (BITS) {
       const Words x = philox(uint64_t(j), a.k, a.key0, a.key1);
-      uint32_t* o = static_cast<uint32_t*>(a.out0);
+      uint32_t* o = static_cast<uint32_t*>(a.out[0]);
 #pragma unroll
       for (int v = 0; v < 4; ++v)
         if (e0 + v < a.n) o[e0 + v] = x.w[v];
     } else {
       T z[Block<T>::W];
       normals(uint64_t(j), a.k, a.key0, a.key1, z);
-      T* o = static_cast<T*>(a.out0);
+      T* o = static_cast<T*>(a.out[0]);
 #pragma unroll
       for (int v = 0; v < Block<T>::W; ++v)
         if (e0 + v < a.n) o[e0 + v] = z[v];
@@ -301,123 +244,6 @@ int check_common(const char* who, int64_t n, int64_t k, int dtype) {
   return XDE_OK;
 }
 
-SdeArgs make_args(int64_t n, int W, double dt, double s, uint64_t seed, int64_t k) {
-  SdeArgs a;
-  memset(&a, 0, sizeof(a));
-  a.n = n;
-  a.nblk = (n + W - 1) / W;
-  a.dt = dt;
-  a.s = s;
-  a.key0 = uint32_t(seed);
-  a.key1 = uint32_t(seed >> 32);
-  a.k = uint32_t(k);
-  return a;
-}
-
-}  // namespace
-
-extern "C" {
-
-int xde_sde_em_step(void* y1, const void* y0, const void* f, const void* g, int64_t n, double dt, double s, uint64_t seed,
-                    int64_t k, int dtype, void* stream) {
-  if (!y1 || !y0 || !f || !g) return fail(XDE_EBADARG, "xde_sde_em_step: null pointer");
-  if (int rc = check_common("xde_sde_em_step", n, k, dtype)) return rc;
-  const size_t esz = dtype == XDE_F32 ? 4 : 8;
-  const void* ptrs[4] = {y1, y0, f, g};
-  bool vec = true;
-  for (const void* p : ptrs) {
-    if (!aligned_to(p, esz)) return fail(XDE_EBADARG, "xde_sde_em_step: operand not aligned to its element type");
-    vec = vec && aligned16(p);
-  }
-  if (n == 0) return XDE_OK;
-  SdeArgs a = make_args(n, dtype == XDE_F32 ? 4 : 2, dt, s, seed, k);
-  a.out0 = y1;
-  a.in0 = y0;
-  a.in1 = f;
-  a.in2 = g;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  // (profiled under the fixed-step fuse id: the kernel-id list of xde_hip.h is part of the frozen ABI — an EM step is the SDE's fuse)
-  ProfScope prof(XDE_KID_COMBINE_FUSE, 4.0 * double(n) * double(esz));
-  const dim3 gr = grid_for(a.nblk), b(kBlock);
-  if (dtype == XDE_F32) {
-    if (vec) XDE_LAUNCH((xde_sde_em_step_kernel<float, true>), gr, b, st, prof, a);
-    else XDE_LAUNCH((xde_sde_em_step_kernel<float, false>), gr, b, st, prof, a);
-  } else {
-    if (vec) XDE_LAUNCH((xde_sde_em_step_kernel<double, true>), gr, b, st, prof, a);
-    else XDE_LAUNCH((xde_sde_em_step_kernel<double, false>), gr, b, st, prof, a);
-  }
-  HIP_TRY(hipGetLastError());
-  return XDE_OK;
-}
-
-}  // extern "C"
-
-namespace {
-
-template <typename T, bool VEC>
-void launch_backward(const SdeArgs& a, bool gf, bool gg, dim3 gr, dim3 b, hipStream_t st, ProfScope& prof) {
-  if (gf && gg) XDE_LAUNCH((xde_sde_em_backward_kernel<T, VEC, true, true>), gr, b, st, prof, a);
-  else if (gf) XDE_LAUNCH((xde_sde_em_backward_kernel<T, VEC, true, false>), gr, b, st, prof, a);
-  else XDE_LAUNCH((xde_sde_em_backward_kernel<T, VEC, false, true>), gr, b, st, prof, a);
-}
-
-}  // namespace
-
-extern "C" {
-
-int xde_sde_em_backward(void* gf, void* gg, const void* gy1, int64_t n, double dt, double s, uint64_t seed, int64_t k, int dtype,
-                        void* stream) {
-  if (!gy1) return fail(XDE_EBADARG, "xde_sde_em_backward: null pointer (gy1)");
-  if (int rc = check_common("xde_sde_em_backward", n, k, dtype)) return rc;
-  const size_t esz = dtype == XDE_F32 ? 4 : 8;
-  const void* ptrs[3] = {gy1, gf, gg};
-  bool vec = true;
-  for (const void* p : ptrs) {
-    if (!p) continue;
-    if (!aligned_to(p, esz)) return fail(XDE_EBADARG, "xde_sde_em_backward: operand not aligned to its element type");
-    vec = vec && aligned16(p);
-  }
-  if (n == 0 || (!gf && !gg)) return XDE_OK;
-  SdeArgs a = make_args(n, dtype == XDE_F32 ? 4 : 2, dt, s, seed, k);
-  a.out0 = gf;
-  a.out1 = gg;
-  a.in0 = gy1;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  ProfScope prof(XDE_KID_COMBINE, double(1 + (gf ? 1 : 0) + (gg ? 1 : 0)) * double(n) * double(esz));
-  const dim3 gr = grid_for(a.nblk), b(kBlock);
-  if (dtype == XDE_F32) vec ? launch_backward<float, true>(a, gf, gg, gr, b, st, prof) : launch_backward<float, false>(a, gf, gg, gr, b, st, prof);
-  else vec ? launch_backward<double, true>(a, gf, gg, gr, b, st, prof) : launch_backward<double, false>(a, gf, gg, gr, b, st, prof);
-  HIP_TRY(hipGetLastError());
-  return XDE_OK;
-}
-
-int xde_sde_noise(void* out, int64_t n, uint64_t seed, int64_t k, int mode, int dtype, void* stream) {
-  if (!out) return fail(XDE_EBADARG, "xde_sde_noise: null pointer");
-  if (mode != XDE_NOISE_NORMAL && mode != XDE_NOISE_BITS) return fail(XDE_EBADARG, "xde_sde_noise: bad mode");
-  if (int rc = check_common("xde_sde_noise", n, k, dtype)) return rc;
-  const bool bits = mode == XDE_NOISE_BITS;
-  const size_t esz = bits ? 4 : (dtype == XDE_F32 ? 4 : 8);
-  if (!aligned_to(out, esz)) return fail(XDE_EBADARG, "xde_sde_noise: output not aligned to its element type");
-  if (n == 0) return XDE_OK;
-  SdeArgs a = make_args(n, bits ? 4 : (dtype == XDE_F32 ? 4 : 2), 0.0, 0.0, seed, k);
-  a.out0 = out;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  ProfScope prof(XDE_KID_COMBINE, double(n) * double(esz));
-  const dim3 gr = grid_for(a.nblk), b(kBlock);
-  if (bits) XDE_LAUNCH((xde_sde_noise_kernel<float, true>), gr, b, st, prof, a);
-  else if (dtype == XDE_F32) XDE_LAUNCH((xde_sde_noise_kernel<float, false>), gr, b, st, prof, a);
-  else XDE_LAUNCH((xde_sde_noise_kernel<double, false>), gr, b, st, prof, a);
-  HIP_TRY(hipGetLastError());
-  return XDE_OK;
-}
-
-}  // extern "C"
-
-// ------------------------------------------------------------------------------------------
-// Milstein (derivative-free, Ito, diagonal noise): support point, step, and their backwards
-// ------------------------------------------------------------------------------------------
-namespace {
-
 // element alignment of every non-null operand; *vec = all of them 16-byte aligned
 int check_operands(const char* who, const void* const* ptrs, int count, size_t esz, bool* vec) {
   *vec = true;
@@ -429,130 +255,125 @@ int check_operands(const char* who, const void* const* ptrs, int count, size_t e
   return XDE_OK;
 }
 
-template <typename T, bool VEC>
-void launch_support_backward(const SdeArgs& a, bool gf, bool gg, dim3 gr, dim3 b, hipStream_t st, ProfScope& prof) {
-  if (gf && gg) XDE_LAUNCH((xde_sde_em_backward_kernel<T, VEC, true, true, false>), gr, b, st, prof, a);
-  else if (gf) XDE_LAUNCH((xde_sde_em_backward_kernel<T, VEC, true, false, false>), gr, b, st, prof, a);
-  else XDE_LAUNCH((xde_sde_em_backward_kernel<T, VEC, false, true, false>), gr, b, st, prof, a);
+SdeArgs make_args(int64_t n, int W, double dt, double s, double c, uint64_t seed, int64_t k) {
+  SdeArgs a;
+  memset(&a, 0, sizeof(a));
+  a.n = n;
+  a.nblk = (n + W - 1) / W;
+  a.dt = dt;
+  a.s = s;
+  a.c = c;
+  a.key0 = uint32_t(seed);
+  a.key1 = uint32_t(seed >> 32);
+  a.k = uint32_t(k);
+  return a;
 }
 
-template <typename T, bool VEC>
-void launch_milstein_backward(const SdeArgs& a, int mask, dim3 gr, dim3 b, hipStream_t st, ProfScope& prof) {
-  switch (mask) {  // bit 0: gf, bit 1: gg, bit 2: ggb
-    case 1: XDE_LAUNCH((xde_sde_milstein_backward_kernel<T, VEC, true, false, false>), gr, b, st, prof, a); break;
-    case 2: XDE_LAUNCH((xde_sde_milstein_backward_kernel<T, VEC, false, true, false>), gr, b, st, prof, a); break;
-    case 3: XDE_LAUNCH((xde_sde_milstein_backward_kernel<T, VEC, true, true, false>), gr, b, st, prof, a); break;
-    case 4: XDE_LAUNCH((xde_sde_milstein_backward_kernel<T, VEC, false, false, true>), gr, b, st, prof, a); break;
-    case 5: XDE_LAUNCH((xde_sde_milstein_backward_kernel<T, VEC, true, false, true>), gr, b, st, prof, a); break;
-    case 6: XDE_LAUNCH((xde_sde_milstein_backward_kernel<T, VEC, false, true, true>), gr, b, st, prof, a); break;
-    default: XDE_LAUNCH((xde_sde_milstein_backward_kernel<T, VEC, true, true, true>), gr, b, st, prof, a); break;
+// runtime output mask -> the kernel compiled for it (masks 1 .. 2^NO - 1)
+template <typename T, bool VEC, bool NOISE, class Op, int MASK = 1>
+void launch_masked(int mask, const SdeArgs& a, dim3 gr, hipStream_t st, ProfScope& prof) {
+  if (mask == MASK) XDE_LAUNCH((xde_sde_step_kernel<T, VEC, NOISE, Op, MASK>), gr, dim3(kBlock), st, prof, a);
+  else if constexpr (MASK + 1 < (1 << Op::NO)) launch_masked<T, VEC, NOISE, Op, MASK + 1>(mask, a, gr, st, prof);
+}
+
+// The host side of every step entry point: checks in the order null pointers, n / dtype / k, alignment; then nothing to do; then one
+// launch.  A backward (`backward`, with `cotangent` the name of its single input in the error text) may leave outputs null: they are
+// skipped; a forward requires every pointer.  Profiled under `kid` with the bytes the launch moves: every input once, every written
+// output once.
+template <class Op, bool NOISE = true>
+int sde_launch(const char* who, int kid, bool backward, const char* cotangent, void* const (&outs)[Op::NO],
+               const void* const (&ins)[Op::NI], int64_t n, double dt, double s, double c, uint64_t seed, int64_t k, int dtype, void* stream) {
+  const void* ptrs[Op::NO + Op::NI];
+  int mask = 0, written = 0;
+  bool null = false;
+  for (int i = 0; i < Op::NO; ++i) {
+    ptrs[i] = outs[i];
+    if (outs[i]) {
+      mask |= 1 << i;
+      ++written;
+    } else if (!backward) {
+      null = true;
+    }
   }
+  for (int i = 0; i < Op::NI; ++i) {
+    ptrs[Op::NO + i] = ins[i];
+    if (!ins[i]) null = true;
+  }
+  if (null) return fail(XDE_EBADARG, std::string(who) + ": null pointer" + (backward ? " (" + std::string(cotangent) + ")" : ""));
+  if (int rc = check_common(who, n, k, dtype)) return rc;
+  const size_t esz = dtype == XDE_F32 ? 4 : 8;
+  bool vec;
+  if (int rc = check_operands(who, ptrs, Op::NO + Op::NI, esz, &vec)) return rc;
+  if (n == 0 || !mask) return XDE_OK;
+  SdeArgs a = make_args(n, dtype == XDE_F32 ? 4 : 2, dt, s, c, seed, k);
+  for (int i = 0; i < Op::NO; ++i) a.out[i] = outs[i];
+  for (int i = 0; i < Op::NI; ++i) a.in[i] = ins[i];
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  ProfScope prof(kid, double(Op::NI + written) * double(n) * double(esz));
+  const dim3 gr = grid_for(a.nblk);
+  if (dtype == XDE_F32) vec ? launch_masked<float, true, NOISE, Op>(mask, a, gr, st, prof) : launch_masked<float, false, NOISE, Op>(mask, a, gr, st, prof);
+  else vec ? launch_masked<double, true, NOISE, Op>(mask, a, gr, st, prof) : launch_masked<double, false, NOISE, Op>(mask, a, gr, st, prof);
+  HIP_TRY(hipGetLastError());
+  return XDE_OK;
 }
 
 }  // namespace
 
 extern "C" {
 
+// (profiled under the fixed-step fuse id: the kernel-id list of xde_hip.h is part of the frozen ABI — an EM step is the SDE's fuse)
+int xde_sde_em_step(void* y1, const void* y0, const void* f, const void* g, int64_t n, double dt, double s, uint64_t seed,
+                    int64_t k, int dtype, void* stream) {
+  return sde_launch<EmStep>("xde_sde_em_step", XDE_KID_COMBINE_FUSE, false, nullptr, {y1}, {y0, f, g}, n, dt, s, 0.0, seed, k, dtype, stream);
+}
+
+int xde_sde_em_backward(void* gf, void* gg, const void* gy1, int64_t n, double dt, double s, uint64_t seed, int64_t k, int dtype,
+                        void* stream) {
+  return sde_launch<EmBackward>("xde_sde_em_backward", XDE_KID_COMBINE, true, "gy1", {gf, gg}, {gy1}, n, dt, s, 0.0, seed, k, dtype, stream);
+}
+
+// Milstein (derivative-free, Ito, diagonal noise): support point, step, and their backwards.
+// (the support point is a stage input: the stage combines' id)
 int xde_sde_milstein_support(void* yb, const void* y0, const void* f, const void* g, int64_t n, double dt, double s, int dtype,
                              void* stream) {
-  if (!yb || !y0 || !f || !g) return fail(XDE_EBADARG, "xde_sde_milstein_support: null pointer");
-  if (int rc = check_common("xde_sde_milstein_support", n, 0, dtype)) return rc;
-  const size_t esz = dtype == XDE_F32 ? 4 : 8;
-  const void* ptrs[4] = {yb, y0, f, g};
-  bool vec;
-  if (int rc = check_operands("xde_sde_milstein_support", ptrs, 4, esz, &vec)) return rc;
-  if (n == 0) return XDE_OK;
-  SdeArgs a = make_args(n, dtype == XDE_F32 ? 4 : 2, dt, s, 0, 0);
-  a.out0 = yb;
-  a.in0 = y0;
-  a.in1 = f;
-  a.in2 = g;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  ProfScope prof(XDE_KID_COMBINE, 4.0 * double(n) * double(esz));  // (a stage input: the stage combines' id)
-  const dim3 gr = grid_for(a.nblk), b(kBlock);
-  if (dtype == XDE_F32) {
-    if (vec) XDE_LAUNCH((xde_sde_em_step_kernel<float, true, false>), gr, b, st, prof, a);
-    else XDE_LAUNCH((xde_sde_em_step_kernel<float, false, false>), gr, b, st, prof, a);
-  } else {
-    if (vec) XDE_LAUNCH((xde_sde_em_step_kernel<double, true, false>), gr, b, st, prof, a);
-    else XDE_LAUNCH((xde_sde_em_step_kernel<double, false, false>), gr, b, st, prof, a);
-  }
-  HIP_TRY(hipGetLastError());
-  return XDE_OK;
+  return sde_launch<EmStep, false>("xde_sde_milstein_support", XDE_KID_COMBINE, false, nullptr, {yb}, {y0, f, g}, n, dt, s, 0.0, 0, 0, dtype,
+                                   stream);
 }
 
 int xde_sde_milstein_support_backward(void* gf, void* gg, const void* gyb, int64_t n, double dt, double s, int dtype, void* stream) {
-  if (!gyb) return fail(XDE_EBADARG, "xde_sde_milstein_support_backward: null pointer (gyb)");
-  if (int rc = check_common("xde_sde_milstein_support_backward", n, 0, dtype)) return rc;
-  const size_t esz = dtype == XDE_F32 ? 4 : 8;
-  const void* ptrs[3] = {gyb, gf, gg};
-  bool vec;
-  if (int rc = check_operands("xde_sde_milstein_support_backward", ptrs, 3, esz, &vec)) return rc;
-  if (n == 0 || (!gf && !gg)) return XDE_OK;
-  SdeArgs a = make_args(n, dtype == XDE_F32 ? 4 : 2, dt, s, 0, 0);
-  a.out0 = gf;
-  a.out1 = gg;
-  a.in0 = gyb;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  ProfScope prof(XDE_KID_COMBINE, double(1 + (gf ? 1 : 0) + (gg ? 1 : 0)) * double(n) * double(esz));
-  const dim3 gr = grid_for(a.nblk), b(kBlock);
-  if (dtype == XDE_F32) vec ? launch_support_backward<float, true>(a, gf, gg, gr, b, st, prof) : launch_support_backward<float, false>(a, gf, gg, gr, b, st, prof);
-  else vec ? launch_support_backward<double, true>(a, gf, gg, gr, b, st, prof) : launch_support_backward<double, false>(a, gf, gg, gr, b, st, prof);
-  HIP_TRY(hipGetLastError());
-  return XDE_OK;
+  return sde_launch<EmBackward, false>("xde_sde_milstein_support_backward", XDE_KID_COMBINE, true, "gyb", {gf, gg}, {gyb}, n, dt, s, 0.0, 0, 0,
+                                       dtype, stream);
 }
 
+// (the SDE's fuse, as the EM step)
 int xde_sde_milstein_step(void* y1, const void* y0, const void* f, const void* g, const void* gb, int64_t n, double dt, double s,
                           double c, uint64_t seed, int64_t k, int dtype, void* stream) {
-  if (!y1 || !y0 || !f || !g || !gb) return fail(XDE_EBADARG, "xde_sde_milstein_step: null pointer");
-  if (int rc = check_common("xde_sde_milstein_step", n, k, dtype)) return rc;
-  const size_t esz = dtype == XDE_F32 ? 4 : 8;
-  const void* ptrs[5] = {y1, y0, f, g, gb};
-  bool vec;
-  if (int rc = check_operands("xde_sde_milstein_step", ptrs, 5, esz, &vec)) return rc;
-  if (n == 0) return XDE_OK;
-  SdeArgs a = make_args(n, dtype == XDE_F32 ? 4 : 2, dt, s, seed, k);
-  a.c = c;
-  a.out0 = y1;
-  a.in0 = y0;
-  a.in1 = f;
-  a.in2 = g;
-  a.in3 = gb;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  ProfScope prof(XDE_KID_COMBINE_FUSE, 5.0 * double(n) * double(esz));  // (the SDE's fuse, as the EM step)
-  const dim3 gr = grid_for(a.nblk), b(kBlock);
-  if (dtype == XDE_F32) {
-    if (vec) XDE_LAUNCH((xde_sde_milstein_step_kernel<float, true>), gr, b, st, prof, a);
-    else XDE_LAUNCH((xde_sde_milstein_step_kernel<float, false>), gr, b, st, prof, a);
-  } else {
-    if (vec) XDE_LAUNCH((xde_sde_milstein_step_kernel<double, true>), gr, b, st, prof, a);
-    else XDE_LAUNCH((xde_sde_milstein_step_kernel<double, false>), gr, b, st, prof, a);
-  }
-  HIP_TRY(hipGetLastError());
-  return XDE_OK;
+  return sde_launch<MilsteinStep>("xde_sde_milstein_step", XDE_KID_COMBINE_FUSE, false, nullptr, {y1}, {y0, f, g, gb}, n, dt, s, c, seed, k,
+                                  dtype, stream);
 }
 
 int xde_sde_milstein_backward(void* gf, void* gg, void* ggb, const void* gy1, int64_t n, double dt, double s, double c, uint64_t seed,
                               int64_t k, int dtype, void* stream) {
-  if (!gy1) return fail(XDE_EBADARG, "xde_sde_milstein_backward: null pointer (gy1)");
-  if (int rc = check_common("xde_sde_milstein_backward", n, k, dtype)) return rc;
-  const size_t esz = dtype == XDE_F32 ? 4 : 8;
-  const void* ptrs[4] = {gy1, gf, gg, ggb};
-  bool vec;
-  if (int rc = check_operands("xde_sde_milstein_backward", ptrs, 4, esz, &vec)) return rc;
-  const int mask = (gf ? 1 : 0) | (gg ? 2 : 0) | (ggb ? 4 : 0);
-  if (n == 0 || !mask) return XDE_OK;
-  SdeArgs a = make_args(n, dtype == XDE_F32 ? 4 : 2, dt, s, seed, k);
-  a.c = c;
-  a.out0 = gf;
-  a.out1 = gg;
-  a.out2 = ggb;
-  a.in0 = gy1;
+  return sde_launch<MilsteinBackward>("xde_sde_milstein_backward", XDE_KID_COMBINE, true, "gy1", {gf, gg, ggb}, {gy1}, n, dt, s, c, seed, k,
+                                      dtype, stream);
+}
+
+int xde_sde_noise(void* out, int64_t n, uint64_t seed, int64_t k, int mode, int dtype, void* stream) {
+  if (!out) return fail(XDE_EBADARG, "xde_sde_noise: null pointer");
+  if (mode != XDE_NOISE_NORMAL && mode != XDE_NOISE_BITS) return fail(XDE_EBADARG, "xde_sde_noise: bad mode");
+  if (int rc = check_common("xde_sde_noise", n, k, dtype)) return rc;
+  const bool bits = mode == XDE_NOISE_BITS;
+  const size_t esz = bits ? 4 : (dtype == XDE_F32 ? 4 : 8);
+  if (!aligned_to(out, esz)) return fail(XDE_EBADARG, "xde_sde_noise: output not aligned to its element type");
+  if (n == 0) return XDE_OK;
+  SdeArgs a = make_args(n, bits ? 4 : (dtype == XDE_F32 ? 4 : 2), 0.0, 0.0, 0.0, seed, k);
+  a.out[0] = out;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  ProfScope prof(XDE_KID_COMBINE, double(1 + (gf ? 1 : 0) + (gg ? 1 : 0) + (ggb ? 1 : 0)) * double(n) * double(esz));
+  ProfScope prof(XDE_KID_COMBINE, double(n) * double(esz));
   const dim3 gr = grid_for(a.nblk), b(kBlock);
-  if (dtype == XDE_F32) vec ? launch_milstein_backward<float, true>(a, mask, gr, b, st, prof) : launch_milstein_backward<float, false>(a, mask, gr, b, st, prof);
-  else vec ? launch_milstein_backward<double, true>(a, mask, gr, b, st, prof) : launch_milstein_backward<double, false>(a, mask, gr, b, st, prof);
+  if (bits) XDE_LAUNCH((xde_sde_noise_kernel<float, true>), gr, b, st, prof, a);
+  else if (dtype == XDE_F32) XDE_LAUNCH((xde_sde_noise_kernel<float, false>), gr, b, st, prof, a);
+  else XDE_LAUNCH((xde_sde_noise_kernel<double, false>), gr, b, st, prof, a);
   HIP_TRY(hipGetLastError());
   return XDE_OK;
 }

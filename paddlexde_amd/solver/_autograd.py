@@ -11,6 +11,22 @@ from torch.autograd.function import once_differentiable
 from .. import _hip
 
 
+def _cotangent(g):
+    """The incoming cotangent as a launch operand: contiguous and 16-byte aligned."""
+    g = g.contiguous()
+    return g.clone() if g.data_ptr() % 16 else g
+
+
+def _sde_backward(launch, g, needs, meta):
+    """The backward of an SDE step node: ``needs`` = (y0, then the operands of ``launch``'s outputs).  The cotangent of y0 is ``g``
+    itself; the wanted others are allocated and written by one ``launch(*outs, g, *meta)`` (None: skipped), if any is wanted."""
+    g = _cotangent(g)
+    outs = [torch.empty_like(g) if need else None for need in needs[1:]]
+    if any(o is not None for o in outs):
+        launch(*outs, g, *meta)
+    return (g if needs[0] else None, *outs)
+
+
 class CombineFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, backend, coef, mode, scale, dt, damp, y0, *ks):
@@ -36,9 +52,7 @@ class CombineFn(torch.autograd.Function):
             # out = scale * sum_j w_j fuse(k_j, dt, y0)
             fy0 = scale * sum(coef) * g_damp
             fk = [scale * w * dt * g_damp for w in coef]
-        g = g.contiguous()
-        if g.data_ptr() % 16:
-            g = g.clone()
+        g = _cotangent(g)
         factors = [fy0] + fk
         outs, todo_o, todo_f = [], [], []
         for need, f in zip(ctx.needs, factors):
@@ -85,9 +99,7 @@ class InterpRowsFn(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, g):
         need = ctx.needs_input_grad[3:7]
-        g = g.contiguous()
-        if g.data_ptr() % 16:
-            g = g.clone()
+        g = _cotangent(g)
         like = g[0]
         outs = [torch.empty_like(like) if need[0] else None, torch.empty_like(like) if need[1] else None, None,
                 torch.empty_like(like) if need[2] else None, torch.empty_like(like) if need[3] else None]
@@ -111,21 +123,7 @@ class SdeEulerFn(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
-        need_y0, need_f, need_g = ctx.needs_input_grad[5:8]
-        g = g.contiguous()
-        if g.data_ptr() % 16:
-            g = g.clone()
-        gf = torch.empty_like(g) if need_f else None
-        gg = torch.empty_like(g) if need_g else None
-        if gf is not None or gg is not None:
-            dt, s, seed, k = ctx.meta
-            ctx.backend._sde_em_backward(gf, gg, g, dt, s, seed, k)
-        return (None, None, None, None, None, g if need_y0 else None, gf, gg)
-
-
-def _cotangent(g):
-    g = g.contiguous()
-    return g.clone() if g.data_ptr() % 16 else g
+        return (None,) * 5 + _sde_backward(ctx.backend._sde_em_backward, g, ctx.needs_input_grad[5:8], ctx.meta)
 
 
 class SdeSupportFn(torch.autograd.Function):
@@ -142,13 +140,7 @@ class SdeSupportFn(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
-        need_y0, need_f, need_g = ctx.needs_input_grad[3:6]
-        g = _cotangent(g)
-        gf = torch.empty_like(g) if need_f else None
-        gg = torch.empty_like(g) if need_g else None
-        if gf is not None or gg is not None:
-            ctx.backend._sde_milstein_support_backward(gf, gg, g, *ctx.meta)
-        return (None, None, None, g if need_y0 else None, gf, gg)
+        return (None,) * 3 + _sde_backward(ctx.backend._sde_milstein_support_backward, g, ctx.needs_input_grad[3:6], ctx.meta)
 
 
 class SdeMilsteinFn(torch.autograd.Function):
@@ -167,11 +159,4 @@ class SdeMilsteinFn(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
-        need_y0, need_f, need_g, need_gb = ctx.needs_input_grad[6:10]
-        g = _cotangent(g)
-        gf = torch.empty_like(g) if need_f else None
-        gg = torch.empty_like(g) if need_g else None
-        ggb = torch.empty_like(g) if need_gb else None
-        if gf is not None or gg is not None or ggb is not None:
-            ctx.backend._sde_milstein_backward(gf, gg, ggb, g, *ctx.meta)
-        return (None, None, None, None, None, None, g if need_y0 else None, gf, gg, ggb)
+        return (None,) * 6 + _sde_backward(ctx.backend._sde_milstein_backward, g, ctx.needs_input_grad[6:10], ctx.meta)

@@ -238,19 +238,29 @@ class FixedSolver(metaclass=abc.ABCMeta):
         self.backend.stage_combine(out, y0, ks, coef, mode, scale=scale, dt_host=float(dt), damping=damp, out2=part, coef2=emit)
         return out if emit is None else (out, part)
 
+    def _sde_prologue(self, t0, dtt, y0, dt):
+        """What both SDE steps start from: drift and diffusion at ``(t0, y0)`` as operands, ``dt``, ``s = sqrt(|dt|)`` and
+        ``c = 0.5/sqrt(|dt|)`` (0 for a zero-length step) computed in float64 and rounded to the state dtype, the grid step ``k``, and
+        whether an operand is being differentiated.  Returns ``(f, g, dt, s, c, k, grad)``, the scalars as Python floats."""
+        self.nfe += 1
+        f, g = self.move(t0, dtt, y0)
+        f, g = as_operand(f, like=y0), as_operand(g, like=y0)
+        T = np_dtype(y0.dtype)
+        root = np.sqrt(abs(np.float64(dt)))
+        c = T(0.5 / root) if root > 0 else T(0.0)
+        k = self._k if self._k is not None else 0  # (a step() call outside integrate() is the first step of a walk)
+        grad = torch.is_grad_enabled() and (y0.requires_grad or f.requires_grad or g.requires_grad)
+        return f, g, float(dt), float(T(root)), float(c), k, grad
+
     def _em_step(self, t0, dtt, y0, dt):
         """One Ito Euler-Maruyama step of a BaseSDE: ``y1 = (y0 + f*dt) + g*(s*Z)``, ``s = sqrt(|dt|)`` in the state dtype, Z the
         normals of (xde.seed, grid step k) — one xde_sde_em_step launch (SdeEulerFn when an operand is differentiated).  Returns
         ``(y1, f)``."""
-        self.nfe += 1
-        f, g = self.move(t0, dtt, y0)
-        f, g = as_operand(f, like=y0), as_operand(g, like=y0)
-        s = np_dtype(y0.dtype)(np.sqrt(abs(np.float64(dt))))
-        k = self._k if self._k is not None else 0  # (a step() call outside integrate() is the first step of a walk)
-        if torch.is_grad_enabled() and (y0.requires_grad or f.requires_grad or g.requires_grad):
-            return SdeEulerFn.apply(self.backend, float(dt), float(s), self.xde.seed, k, y0, f, g), f
+        f, g, dt, s, _, k, grad = self._sde_prologue(t0, dtt, y0, dt)
+        if grad:
+            return SdeEulerFn.apply(self.backend, dt, s, self.xde.seed, k, y0, f, g), f
         out = self._y1_out if self._y1_out is not None else torch.empty_like(y0)
-        self.backend._sde_em_step(out, y0, f, g, float(dt), float(s), self.xde.seed, k)
+        self.backend._sde_em_step(out, y0, f, g, dt, s, self.xde.seed, k)
         return out, f
 
     def _milstein_step(self, t0, dtt, y0, dt):
@@ -261,23 +271,16 @@ class FixedSolver(metaclass=abc.ABCMeta):
         step (which then returns y0), Z the normals of (xde.seed, grid step k) as in ``_em_step``.  Through SdeSupportFn /
         SdeMilsteinFn when an operand is differentiated.  ``nfe`` counts steps, as Euler's does: one per step, which here stands for
         one drift and two diffusion evaluations.  Returns ``(y1, f)``."""
-        self.nfe += 1
-        f, g = self.move(t0, dtt, y0)
-        f, g = as_operand(f, like=y0), as_operand(g, like=y0)
-        T = np_dtype(y0.dtype)
-        root = np.sqrt(abs(np.float64(dt)))
-        s = T(root)
-        c = T(0.5 / root) if root > 0 else T(0.0)
-        k = self._k if self._k is not None else 0  # (a step() call outside integrate() is the first step of a walk)
-        if torch.is_grad_enabled() and (y0.requires_grad or f.requires_grad or g.requires_grad):
-            yb = SdeSupportFn.apply(self.backend, float(dt), float(s), y0, f, g)
+        f, g, dt, s, c, k, grad = self._sde_prologue(t0, dtt, y0, dt)
+        if grad:
+            yb = SdeSupportFn.apply(self.backend, dt, s, y0, f, g)
             gb = as_operand(self.xde.diffusion(t0, yb), like=y0)
-            return SdeMilsteinFn.apply(self.backend, float(dt), float(s), float(c), self.xde.seed, k, y0, f, g, gb), f
+            return SdeMilsteinFn.apply(self.backend, dt, s, c, self.xde.seed, k, y0, f, g, gb), f
         yb = torch.empty_like(y0)
-        self.backend._sde_milstein_support(yb, y0, f, g, float(dt), float(s))
+        self.backend._sde_milstein_support(yb, y0, f, g, dt, s)
         gb = as_operand(self.xde.diffusion(t0, yb), like=y0)
         out = self._y1_out if self._y1_out is not None else torch.empty_like(y0)
-        self.backend._sde_milstein_step(out, y0, f, g, gb, float(dt), float(s), float(c), self.xde.seed, k)
+        self.backend._sde_milstein_step(out, y0, f, g, gb, dt, s, c, self.xde.seed, k)
         return out, f
 
     def _combine_pre(self, y0, pre, ks, coef, dt, scale, out=None):

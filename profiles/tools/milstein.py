@@ -102,9 +102,10 @@ def merge_kernel_stats(out, path):
     of_copy = {}
     for row in res["kernels"]:
         t = "float" if row["dtype"] == "float32" else "double"
-        pick = {"step": ("xde_sde_milstein_step_kernel<{}, true>".format(t), "step_bytes"),
-                "bwd": ("xde_sde_milstein_backward_kernel<{}, true, true, true, true>".format(t), "bwd_bytes"),
-                "support": ("xde_sde_em_step_kernel<{}, true, false>".format(t), "support_bytes"),
+        # xde_sde_step_kernel<T, VEC, NOISE, formula, output mask> (csrc/xde_sde.hip)
+        pick = {"step": ("xde_sde_step_kernel<{}, true, true, (anonymous namespace)::MilsteinStep, 1>".format(t), "step_bytes"),
+                "bwd": ("xde_sde_step_kernel<{}, true, true, (anonymous namespace)::MilsteinBackward, 7>".format(t), "bwd_bytes"),
+                "support": ("xde_sde_step_kernel<{}, true, false, (anonymous namespace)::EmStep, 1>".format(t), "support_bytes"),
                 "noise": ("xde_sde_noise_kernel<{}, false>".format(t), None)}
         d = {}
         for key, (kname, nbytes) in pick.items():

@@ -1,6 +1,8 @@
 """Test-side restatement of sdeint's noise and step (include/xde_hip_sde.h), in numpy, written from the header's mapping and not from
 the kernel: Philox4x32-10 (Salmon, Moraes, Dror, Shaw, "Parallel random numbers: as easy as 1, 2, 3", SC'11), the uniform mapping,
 Box-Muller in float64, and the Ito Euler-Maruyama walk ``y1 = (y0 + f*dt) + g*(s*Z)`` in the state dtype's op order."""
+import os
+
 import numpy as np
 
 M0, M1 = 0xD2511F53, 0xCD9E8D57
@@ -82,6 +84,16 @@ def normals(n, seed, k, dtype, with_r=False):
 def state_normals(shape, seed, k, dtype):
     """The Z of a state of ``shape`` in its dtype (the float64 Box-Muller rounded once)."""
     return normals(int(np.prod(shape)), seed, k, dtype).astype(dtype).reshape(shape)
+
+
+def wrap_n(dtype):
+    """A size past the step kernels' grid cap (XDE_GRID_BLOCKS, default 2048, at most 4096 workgroups of 256 lanes, W = 4 fp32 or 2 fp64
+    elements a lane): every lane of the capped grid runs its loop once, the first workgroup's lanes a second time, and the 3 elements
+    left over make the second workgroup's first lane (fp64: first two lanes) wrap too, the last on a ragged tail — a vector body, a
+    wrapped second pass and the scalar tail in one launch."""
+    cap = min(int(os.environ.get("XDE_GRID_BLOCKS", 2048)), 4096)
+    W = 16 // np.dtype(dtype).itemsize
+    return cap * 256 * W + 256 * W + 3
 
 
 def s_of(dt, dtype):

@@ -63,6 +63,10 @@ def test_milstein_kernels_equal_numpy_bit_for_bit(dtype, n, misalign):
     yb = _like(y0, misalign)
     be._sde_milstein_support(yb, y0, f, g_in, float(dt), float(s))
     assert np.array_equal(yb.cpu().numpy(), (Y0 + F * dt) + G * s)
+    inplace = _like(y0, misalign)
+    inplace.copy_(y0)
+    be._sde_milstein_support(inplace, inplace, f, g_in, float(dt), float(s))  # (yb may be y0)
+    assert np.array_equal(inplace.cpu().numpy(), (Y0 + F * dt) + G * s)
     for want_f, want_g in ((True, True), (True, False), (False, True)):
         gf, gg = _like(gy, misalign), _like(gy, misalign)
         be._sde_milstein_support_backward(gf if want_f else None, gg if want_g else None, gy, float(dt), float(s))
@@ -82,13 +86,36 @@ def test_milstein_kernels_equal_numpy_bit_for_bit(dtype, n, misalign):
     be._sde_em_step(em, y0, f, g_in, float(dt), float(s), seed, k)
     be._sde_milstein_step(mil, y0, f, g_in, g_in, float(dt), float(s), float(c), seed, k)
     assert np.array_equal(em.cpu().numpy(), mil.cpu().numpy())
-    # the backward: all three outputs, then each alone (the others keep their fill)
+    # the backward: all three outputs, then each alone and each pair (the others keep their fill)
     wants = (GY * dt, GY * (w - q), GY * q)
-    for mask in ((1, 1, 1), (1, 0, 0), (0, 1, 0), (0, 0, 1)):
+    for mask in ((1, 1, 1), (1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 0), (1, 0, 1), (0, 1, 1)):
         outs = [_like(gy, misalign) for _ in range(3)]
         be._sde_milstein_backward(*[o if m else None for o, m in zip(outs, mask)], gy, float(dt), float(s), float(c), seed, k)
         for o, m, wnt in zip(outs, mask, wants):
             assert np.array_equal(o.cpu().numpy(), wnt if m else np.full(n, T(SENTINEL))), mask
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
+def test_milstein_kernels_past_the_grid_cap_equal_numpy_bit_for_bit(dtype):
+    """The support point, the step and the full backward at _sde_oracle.wrap_n: the lanes wrap around the capped grid."""
+    be = _hip.get_backend()
+    T = _NPT[dtype]
+    n = SO.wrap_n(T)
+    g = torch.Generator().manual_seed(6)
+    y0, f, g_in, gb, gy = (torch.randn(n, generator=g, dtype=dtype).to(DEV) for _ in range(5))
+    Y0, F, G, GB, GY = (x.cpu().numpy() for x in (y0, f, g_in, gb, gy))
+    seed, k, dt = 0xC0FFEE, 3, T(0.0371)
+    s, c = SO.s_of(dt, T), MO.c_of(dt, T)
+    w, q = MO.correction(dt, _noise(n, seed, k, dtype), T)
+    out = torch.empty_like(y0)
+    be._sde_milstein_support(out, y0, f, g_in, float(dt), float(s))
+    assert np.array_equal(out.cpu().numpy(), (Y0 + F * dt) + G * s)
+    be._sde_milstein_step(out, y0, f, g_in, gb, float(dt), float(s), float(c), seed, k)
+    assert np.array_equal(out.cpu().numpy(), ((Y0 + F * dt) + G * w) + (GB - G) * q)
+    outs = [torch.empty_like(gy) for _ in range(3)]
+    be._sde_milstein_backward(*outs, gy, float(dt), float(s), float(c), seed, k)
+    for o, want in zip(outs, (GY * dt, GY * (w - q), GY * q)):
+        assert np.array_equal(o.cpu().numpy(), want)
 
 
 def test_a_zero_length_step_returns_y0_exactly():

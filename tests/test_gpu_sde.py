@@ -20,6 +20,7 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 _NPT = {torch.float32: np.float32, torch.float64: np.float64}
 _EPS = {torch.float32: 2.0**-24, torch.float64: 2.0**-53}
+SENTINEL = 7.0
 
 
 @pytest.fixture
@@ -122,6 +123,66 @@ def test_em_step_and_backward_equal_numpy_bit_for_bit(dtype, n, misalign):
     only = torch.full_like(gy, 7.0)
     be._sde_em_backward(only, None, gy, float(dt), float(s), seed, k)
     assert np.array_equal(only.cpu().numpy(), GY * dt)
+
+
+def _like(x, misalign):
+    """A sentinel-filled output with x's alignment."""
+    o = torch.full((x.numel() + 1,), SENTINEL, dtype=x.dtype, device=DEV)
+    return o[1:] if misalign else o[:-1]
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
+@pytest.mark.parametrize("n, misalign", [(7, False), (1001, True)])
+def test_em_backward_writes_exactly_the_outputs_it_is_given(dtype, n, misalign):
+    """Every output mask, with the outputs misaligned as well as the cotangent: a skipped output goes in as null, and a buffer standing
+    for it keeps its fill."""
+    be = _hip.get_backend()
+    T = _NPT[dtype]
+    x = torch.randn(n + 1, generator=torch.Generator().manual_seed(n), dtype=dtype).to(DEV)
+    gy = x[1:] if misalign else x[:-1]
+    seed, k, dt = 0x5EED, 17, T(-0.0123)
+    s = SO.s_of(dt, T)
+    GY = gy.cpu().numpy()
+    wants = (GY * dt, GY * (s * _noise(n, seed, k, dtype).cpu().numpy()))
+    for mask in ((1, 1), (1, 0), (0, 1)):
+        outs = [_like(gy, misalign) for _ in range(2)]
+        be._sde_em_backward(*[o if m else None for o, m in zip(outs, mask)], gy, float(dt), float(s), seed, k)
+        for o, m, want in zip(outs, mask, wants):
+            assert np.array_equal(o.cpu().numpy(), want if m else np.full(n, T(SENTINEL))), mask
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
+def test_em_kernels_past_the_grid_cap_equal_numpy_bit_for_bit(dtype):
+    be = _hip.get_backend()
+    T = _NPT[dtype]
+    n = SO.wrap_n(_NPT[dtype])
+    g = torch.Generator().manual_seed(5)
+    y0, f, gd, gy = (torch.randn(n, generator=g, dtype=dtype).to(DEV) for _ in range(4))
+    seed, k, dt = 0xC0FFEE, 3, T(0.0371)
+    s = SO.s_of(dt, T)
+    z = _noise(n, seed, k, dtype).cpu().numpy()
+    Y0, F, G, GY = (x.cpu().numpy() for x in (y0, f, gd, gy))
+    y1 = torch.empty_like(y0)
+    be._sde_em_step(y1, y0, f, gd, float(dt), float(s), seed, k)
+    assert np.array_equal(y1.cpu().numpy(), (Y0 + F * dt) + G * (s * z))
+    gf, gg = torch.empty_like(gy), torch.empty_like(gy)
+    be._sde_em_backward(gf, gg, gy, float(dt), float(s), seed, k)
+    assert np.array_equal(gf.cpu().numpy(), GY * dt) and np.array_equal(gg.cpu().numpy(), GY * (s * z))
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
+def test_the_noise_of_an_element_does_not_depend_on_the_launch_shape(dtype):
+    """The Z that the EM step implies, ``y1 - (y0 + f*dt)`` with g = 1 and s = 1 (so s*Z is Z), is xde_sde_noise's at the same
+    (seed, k), element for element, at the size where the step's lanes wrap around the grid: the step kernel's loop index is the
+    generator's counter.  y0 and f are zero, so that ``(y0 + f*dt) + Z`` rounds nothing away and the difference is Z exactly."""
+    be = _hip.get_backend()
+    n = SO.wrap_n(_NPT[dtype])
+    seed, k, dt = 0xC0FFEE, 9, 0.0371
+    y0, f = torch.zeros(n, dtype=dtype, device=DEV), torch.zeros(n, dtype=dtype, device=DEV)
+    y1 = torch.empty_like(y0)
+    be._sde_em_step(y1, y0, f, torch.ones_like(y0), dt, 1.0, seed, k)
+    implied = y1.cpu().numpy() - (y0.cpu().numpy() + f.cpu().numpy() * _NPT[dtype](dt))
+    assert np.array_equal(implied, _noise(n, seed, k, dtype).cpu().numpy())
 
 
 # ----------------------------------------------------------------------------------------------
