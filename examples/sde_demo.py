@@ -3,12 +3,13 @@
 
 Data: one sample path of ``dy = 2 y A dt + y dW`` (A = [[-0.1, 2], [-2, -0.1]], diagonal noise, the reference's Lambda_f / Lambda_g)
 from y0 = [2, 0] over t in [0, 25], integrated by ``sdeint(..., solver=Euler)`` (Ito Euler-Maruyama).  ``--solver milstein`` trains
-through the strong order 1.0 Milstein steps instead (the data path stays Euler's).  Model (example/sde_demo.py:
+through the strong order 1.0 Milstein steps instead and ``--solver srk`` through the strong order 1.5 SRK steps (the data path stays
+Euler's).  Model (example/sde_demo.py:
 SDEFunc / SDEDiffusion): an MLP drift on y^3 and an MLP diffusion on y^2, both trained by back-propagating through ``sdeint`` on
 windows of ``batch_time`` points of the path (loss: mean |pred - data|).  Every call draws its own Brownian path from torch's
 generator, so ``torch.manual_seed`` makes a run repeatable.
 
-    python examples/sde_demo.py --max-steps 200 [--solver milstein]
+    python examples/sde_demo.py --max-steps 200 [--solver milstein | srk]
 """
 import argparse
 import os
@@ -21,7 +22,7 @@ import torch.nn as nn
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from paddlexde_amd.functional import sdeint  # noqa: E402
-from paddlexde_amd.solver import Euler, Milstein  # noqa: E402
+from paddlexde_amd.solver import SRK, Euler, Milstein  # noqa: E402
 
 TRUE_A = [[-0.1, 2.0], [-2.0, -0.1]]
 
@@ -99,7 +100,7 @@ if __name__ == "__main__":
     ap.add_argument("--max-steps", type=int, default=200)
     ap.add_argument("--batch-size", type=int, default=20)
     ap.add_argument("--batch-time", type=int, default=10)
-    ap.add_argument("--solver", choices=["euler", "milstein"], default="euler")
+    ap.add_argument("--solver", choices=["euler", "milstein", "srk"], default="euler")
     a = ap.parse_args()
-    ls = train(a.max_steps, a.batch_size, a.batch_time, solver={"euler": Euler, "milstein": Milstein}[a.solver])
+    ls = train(a.max_steps, a.batch_size, a.batch_time, solver={"euler": Euler, "milstein": Milstein, "srk": SRK}[a.solver])
     print("first-10 mean loss {:.4f} -> last-10 mean loss {:.4f}".format(sum(ls[:10]) / 10, sum(ls[-10:]) / 10))

@@ -1,5 +1,5 @@
 /*
- * xde_hip_sde.h — entry points of libxde_hip.so for sdeint: Ito Euler-Maruyama and Milstein steps with diagonal noise whose Brownian
+ * xde_hip_sde.h — entry points of libxde_hip.so for sdeint: Ito Euler-Maruyama, Milstein and SRK steps with diagonal noise whose Brownian
  * increments are generated inside the kernel (host side: paddlexde_amd/solver/base_fixed_solver.py, paddlexde_amd/functional/sdeint.py).
  *
  * Same conventions as xde_hip.h (status codes, device pointers borrowed from the caller, `stream` = hipStream_t as void*,
@@ -20,6 +20,9 @@
  *
  * computed in the state dtype with the precise math library (log, sqrt, sincospi(2 u2)).  The noise of an element depends on
  * (seed, k, e) only.  |Z| <= sqrt(48 ln 2) = 5.77 (fp32) and sqrt(106 ln 2) = 8.57 (fp64).
+ *
+ * THE SECOND DRAW.  V[e] is the same mapping at counter = (j & 0xffffffff, j >> 32, k, 1): the last counter word is the draw, 0 for Z
+ * and 1 for V.  Only the SRK entry points take V; Z is the Z of every other entry point.
  *
  * k is a grid step, 0 <= k < 2^32.  Operands are contiguous arrays of n elements of the state dtype; dt is the step's size and
  * s = sqrt(|dt|) rounded to the state dtype by the caller (both converted to the state dtype in the kernel).  The library is built
@@ -69,9 +72,69 @@ int xde_sde_milstein_step(void* y1, const void* y0, const void* f, const void* g
 int xde_sde_milstein_backward(void* gf, void* gg, void* ggb, const void* gy1, int64_t n, double dt, double s, double c, uint64_t seed,
                               int64_t k, int dtype, void* stream);
 
+/*
+ * SRK (Roessler's SRI1W1, "Runge-Kutta methods for the strong approximation of solutions of stochastic differential equations", SIAM J.
+ * Numer. Anal. 48 (2010): derivative-free, strong order 1.5, Ito, diagonal noise: g_i depends on y_i only).  Besides dt, s and
+ * Milstein's c the caller passes c3 = 1 / (6 |dt|) rounded to the state dtype, and c = c3 = 0 when dt == 0 (a zero-length step returns
+ * y0); a = |dt| is taken in the kernel in the state dtype.  Z and V are the two draws of (seed, k).  Per element, in this op order:
+ *
+ *   w = s * Z                                   (the Brownian increment, EM's and Milstein's)
+ *   p = 0.5 * (w + (s * V) * r3)                (I10 / |dt|)
+ *   q = c * (w * w - a)                         (I11 / sqrt|dt|, Milstein's q)
+ *   u = c3 * ((w * w - 3 * a) * w)              (I111 / |dt|)
+ *
+ * r3 = 1 / sqrt(3) = 0.57735026918962576451, and 1/3 = 0.33333333333333333333, 2/3 = 0.66666666666666666667,
+ * 4/3 = 1.3333333333333333333, 5/3 = 1.6666666666666666667 are literals rounded to the state dtype; the other constants are exact.
+ * The caller evaluates a1 = drift(t0, y0), b1 = diffusion(t0, y0) before stage 1, a2 = drift(t0 + 3/4 dt, Y2),
+ * b2 = diffusion(t0 + 1/4 dt, G2), b3 = diffusion(t0 + dt, G3) after it, and b4 = diffusion(t0 + 1/4 dt, G4) after stage 2.
+ *
+ * Stage 1, one launch, 6 n elements moved; no overlap between operands:
+ *   Y2 = (y0 + a1 * (0.75 * dt)) + b1 * (1.5 * p)
+ *   G2 = (y0 + a1 * (0.25 * dt)) + b1 * (0.5 * s)
+ *   G3 = (y0 + a1 * dt) - b1 * s */
+int xde_sde_srk_stage1(void* Y2, void* G2, void* G3, const void* y0, const void* a1, const void* b1, int64_t n, double dt, double s,
+                       uint64_t seed, int64_t k, int dtype, void* stream);
+
+/* Stage 2: G4 = (y0 + a1 * (0.25 * dt)) + ((b1 * -5 + b2 * 3) + b3 * 0.5) * s.  No generator; 6 n; no overlap. */
+int xde_sde_srk_stage2(void* G4, const void* y0, const void* a1, const void* b1, const void* b2, const void* b3, int64_t n, double dt,
+                       double s, int dtype, void* stream);
+
+/* The step, one launch, 8 n:
+ *   e1 = ((-w - q) + 2 * p) - 2 * u        e2 = 4/3 * ((w + q) - p) + 5/3 * u
+ *   e3 = 2/3 * ((w - p) - u) - 1/3 * q     e4 = u
+ *   y1 = ((((y0 + (1/3 * a1 + 2/3 * a2) * dt) + b1 * e1) + b2 * e2) + b3 * e3) + b4 * e4
+ * y1 may be y0; no other overlap. */
+int xde_sde_srk_step(void* y1, const void* y0, const void* a1, const void* a2, const void* b1, const void* b2, const void* b3,
+                     const void* b4, int64_t n, double dt, double s, double c, double c3, uint64_t seed, int64_t k, int dtype,
+                     void* stream);
+
+/* THE BACKWARDS regenerate Z and V from (seed, k).  Outputs may be null by group and are then skipped: a group is given whole or not
+ * at all (a group given in part is refused, right after the null-pointer check and before the n / dtype / k checks), and the generator runs only if a written output depends on it; every group null: nothing
+ * to do.
+ *
+ * Stage 1 (the cotangents of Y2, G2, G3 in; groups: gy | ga1 | gb1):
+ *   gy  = (gY2 + gG2) + gG3
+ *   ga1 = (gY2 * (0.75 * dt) + gG2 * (0.25 * dt)) + gG3 * dt
+ *   gb1 = (gY2 * (1.5 * p) + gG2 * (0.5 * s)) - gG3 * s */
+int xde_sde_srk_stage1_backward(void* gy, void* ga1, void* gb1, const void* gY2, const void* gG2, const void* gG3, int64_t n, double dt,
+                                double s, uint64_t seed, int64_t k, int dtype, void* stream);
+
+/* Stage 2 (groups: ga1 | gb1, gb2, gb3; the cotangent of y0 is gG4 itself; no generator):
+ *   ga1 = gG4 * (0.25 * dt),  gb1 = gG4 * (-5 * s),  gb2 = gG4 * (3 * s),  gb3 = gG4 * (0.5 * s) */
+int xde_sde_srk_stage2_backward(void* ga1, void* gb1, void* gb2, void* gb3, const void* gG4, int64_t n, double dt, double s, int dtype,
+                                void* stream);
+
+/* The step (groups: ga1, ga2 | gb1, gb2, gb3, gb4; the cotangent of y0 is gy1 itself):
+ *   ga1 = gy1 * (1/3 * dt),  ga2 = gy1 * (2/3 * dt),  gb_i = gy1 * e_i */
+int xde_sde_srk_step_backward(void* ga1, void* ga2, void* gb1, void* gb2, void* gb3, void* gb4, const void* gy1, int64_t n, double dt,
+                              double s, double c, double c3, uint64_t seed, int64_t k, int dtype, void* stream);
+
 /* The generator itself (tests, diagnostics): mode XDE_NOISE_NORMAL writes the Z the step kernels above use (the same device
  * function); XDE_NOISE_BITS writes Philox words (dtype is checked but does not change them). */
 int xde_sde_noise(void* out, int64_t n, uint64_t seed, int64_t k, int mode, int dtype, void* stream);
+
+/* The same at counter word 3 = draw: 0 writes what xde_sde_noise writes, bit for bit; 1 writes V (or its words). */
+int xde_sde_noise_draw(void* out, int64_t n, uint64_t seed, int64_t k, int draw, int mode, int dtype, void* stream);
 
 #ifdef __cplusplus
 }

@@ -182,7 +182,7 @@ BACKPROP_PROTOTYPES = {
 GRID_PROTOTYPES = {
     "xde_interp_rows": (_i32, [_vpp, C.POINTER(C.c_int), _dp, _i32, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i64, _i32, _vp]),
 }
-# the entry points of include/xde_hip_sde.h (sdeint's Euler-Maruyama and Milstein steps); bound by load_library() after _bind
+# the entry points of include/xde_hip_sde.h (sdeint's Euler-Maruyama, Milstein and SRK steps); bound by load_library() after _bind
 SDE_PROTOTYPES = {
     "xde_sde_em_step": (_i32, [_vp, _vp, _vp, _vp, _i64, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
     "xde_sde_em_backward": (_i32, [_vp, _vp, _vp, _i64, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
@@ -191,6 +191,13 @@ SDE_PROTOTYPES = {
     "xde_sde_milstein_support_backward": (_i32, [_vp, _vp, _vp, _i64, _dbl, _dbl, _i32, _vp]),
     "xde_sde_milstein_step": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _dbl, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
     "xde_sde_milstein_backward": (_i32, [_vp, _vp, _vp, _vp, _i64, _dbl, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
+    "xde_sde_srk_stage1": (_i32, [_vp] * 6 + [_i64, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
+    "xde_sde_srk_stage2": (_i32, [_vp] * 6 + [_i64, _dbl, _dbl, _i32, _vp]),
+    "xde_sde_srk_step": (_i32, [_vp] * 8 + [_i64, _dbl, _dbl, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
+    "xde_sde_srk_stage1_backward": (_i32, [_vp] * 6 + [_i64, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
+    "xde_sde_srk_stage2_backward": (_i32, [_vp] * 5 + [_i64, _dbl, _dbl, _i32, _vp]),
+    "xde_sde_srk_step_backward": (_i32, [_vp] * 7 + [_i64, _dbl, _dbl, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
+    "xde_sde_noise_draw": (_i32, [_vp, _i64, C.c_uint64, _i64, _i32, _i32, _i32, _vp]),
 }
 SYMBOLS = tuple(PROTOTYPES)
 BACKPROP_SYMBOLS = tuple(BACKPROP_PROTOTYPES)
@@ -781,7 +788,7 @@ class HipBackend:
                                           XDE_INTERP_CUBIC if cubic else XDE_INTERP_LINEAR, outer, chunk, row_stride, dt, st)
             self._check(rc, "xde_interp_rows")
 
-    # -- sdeint's Euler-Maruyama and Milstein steps (include/xde_hip_sde.h) ---------------------------------------------------------------
+    # -- sdeint's Euler-Maruyama, Milstein and SRK steps (include/xde_hip_sde.h) ------------------------------------------------------------
     # Private for the reason _interp_rows is: the public methods are the contract tests/_cpu_double.py mirrors.  Only the fixed-step
     # solvers' SDE path (and its autograd node) call these.
     def _sde_call(self, who, outs, ins, *scalars):
@@ -821,9 +828,39 @@ class HipBackend:
         """``gf = gy1*dt``, ``gg = gy1*(w - q)`` and ``ggb = gy1*q`` (any may be None: skipped), one launch regenerating the forward's Z."""
         self._sde_call("_sde_milstein_backward", (gf, gg, ggb), (gy1,), float(dt), float(s), float(c), int(seed), int(k))
 
-    def _sde_noise(self, out, seed, k, bits=False):
+    def _sde_srk_stage1(self, Y2, G2, G3, y0, a1, b1, dt, s, seed, k):
+        """SRK's first three stage inputs: ``Y2 = (y0 + a1*(0.75*dt)) + b1*(1.5*p)``, ``G2 = (y0 + a1*(0.25*dt)) + b1*(0.5*s)`` and
+        ``G3 = (y0 + a1*dt) - b1*s`` with ``p = 0.5*(s*Z + (s*V)/sqrt(3))``, Z and V the two draws of (``seed``, step ``k``).  One launch."""
+        self._sde_call("_sde_srk_stage1", (Y2, G2, G3), (y0, a1, b1), float(dt), float(s), int(seed), int(k))
+
+    def _sde_srk_stage2(self, G4, y0, a1, b1, b2, b3, dt, s):
+        """SRK's last stage input ``G4 = (y0 + a1*(0.25*dt)) + ((b1*-5 + b2*3) + b3*0.5)*s``.  One launch, no generator."""
+        self._sde_call("_sde_srk_stage2", (G4,), (y0, a1, b1, b2, b3), float(dt), float(s))
+
+    def _sde_srk_step(self, y1, y0, a1, a2, b1, b2, b3, b4, dt, s, c, c3, seed, k):
+        """``y1 = ((((y0 + (a1/3 + 2*a2/3)*dt) + b1*e1) + b2*e2) + b3*e3) + b4*e4`` with the weights e of include/xde_hip_sde.h on
+        the two draws of (``seed``, step ``k``); ``y1`` may be ``y0``.  One launch."""
+        self._sde_call("_sde_srk_step", (y1,), (y0, a1, a2, b1, b2, b3, b4), float(dt), float(s), float(c), float(c3), int(seed), int(k))
+
+    def _sde_srk_stage1_backward(self, gy, ga1, gb1, gY2, gG2, gG3, dt, s, seed, k):
+        """The cotangents of stage 1's ``y0``, ``a1`` and ``b1`` from those of its three outputs (any may be None: skipped), one
+        launch regenerating the forward's draws."""
+        self._sde_call("_sde_srk_stage1_backward", (gy, ga1, gb1), (gY2, gG2, gG3), float(dt), float(s), int(seed), int(k))
+
+    def _sde_srk_stage2_backward(self, ga1, gb1, gb2, gb3, gG4, dt, s):
+        """The cotangents of stage 2's ``a1`` and of its ``b1, b2, b3`` (the drift one, or the diffusion three together, may be None:
+        skipped), one launch."""
+        self._sde_call("_sde_srk_stage2_backward", (ga1, gb1, gb2, gb3), (gG4,), float(dt), float(s))
+
+    def _sde_srk_step_backward(self, ga1, ga2, gb1, gb2, gb3, gb4, gy1, dt, s, c, c3, seed, k):
+        """The cotangents of the step's ``a1, a2`` and of its ``b1 .. b4`` (the drift two together, or the diffusion four together, may
+        be None: skipped), one launch regenerating the forward's draws."""
+        self._sde_call("_sde_srk_step_backward", (ga1, ga2, gb1, gb2, gb3, gb4), (gy1,), float(dt), float(s), float(c), float(c3),
+                       int(seed), int(k))
+
+    def _sde_noise(self, out, seed, k, bits=False, draw=0):
         """The generator's output for (``seed``, step ``k``) into the contiguous ``out``: the normals Z (``out``'s dtype), or with
-        ``bits`` the raw Philox words (``out`` int32 / uint32, one word per element)."""
+        ``bits`` the raw Philox words (``out`` int32 / uint32, one word per element).  ``draw=1``: the second draw, V."""
         self._require_device(out)
         if not out.is_contiguous():
             raise XdeError("_sde_noise: out must be contiguous")
@@ -833,6 +870,10 @@ class HipBackend:
             mode, dt = XDE_NOISE_BITS, XDE_F32
         else:
             mode, dt = XDE_NOISE_NORMAL, dtype_code(out.dtype)
+        if draw:
+            rc = self.lib.xde_sde_noise_draw(out.data_ptr(), out.numel(), int(seed), int(k), int(draw), mode, dt, self._stream(out))
+            self._check(rc, "xde_sde_noise_draw")
+            return
         rc = self.lib.xde_sde_noise(out.data_ptr(), out.numel(), int(seed), int(k), mode, dt, self._stream(out))
         self._check(rc, "xde_sde_noise")
 

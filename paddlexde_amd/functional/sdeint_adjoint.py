@@ -8,7 +8,7 @@ ran.  The name is kept so that ``from paddlexde_amd.functional import sdeint_adj
 
 _MESSAGE = (
     "sdeint_adjoint is not implemented (the stochastic adjoint needs a Brownian path that can be queried backwards in time); "
-    "differentiate through sdeint(..., solver=Euler) or sdeint(..., solver=Milstein) instead"
+    "differentiate through sdeint(..., solver=Euler) or sdeint(..., solver=Milstein) or SRK instead"
 )
 
 

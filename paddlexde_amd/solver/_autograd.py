@@ -1,4 +1,4 @@
-"""Autograd nodes around the step kernels (xde_stage_combine, xde_interp_rows, xde_sde_em_step, xde_sde_milstein_step) for discretise-then-optimise training.
+"""Autograd nodes around the step kernels (xde_stage_combine, xde_interp_rows, xde_sde_em_step, xde_sde_milstein_step, xde_sde_srk_*) for discretise-then-optimise training.
 
 The reference trains by back-propagating through its eager solver ops (example/ode_demo.py:51-53:
 ``pred_y = odeint(func, batch_y0, t_span, solver=RK4); loss.backward()``).  Here the forward is one combine launch
@@ -160,3 +160,76 @@ class SdeMilsteinFn(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, g):
         return (None,) * 6 + _sde_backward(ctx.backend._sde_milstein_backward, g, ctx.needs_input_grad[6:10], ctx.meta)
+
+
+def _sde_group_backward(launch, gs, needs, groups, meta):
+    """The backward of an SRK node: ``needs`` = the operands of ``launch``'s outputs, ``groups`` the runs of them that the launch
+    writes or skips together.  The outputs of every group with a wanted member are allocated and written by one
+    ``launch(*outs, *gs, *meta)`` (None: skipped), if any is wanted; only the wanted ones are handed on."""
+    outs = []
+    for lo, hi in groups:
+        want = any(needs[lo:hi])
+        outs += [torch.empty_like(gs[0]) if want else None for _ in range(lo, hi)]
+    if any(o is not None for o in outs):
+        launch(*outs, *gs, *meta)
+    return tuple(o if need else None for o, need in zip(outs, needs))
+
+
+class SdeSrkStage1Fn(torch.autograd.Function):
+    """SRK's stage inputs ``Y2, G2, G3`` (``HipBackend._sde_srk_stage1``) as one autograd node with three outputs.  The node keeps only
+    ``(dt, s, seed, k)``: backward regenerates Z and V from the same counters in the launch that turns the three cotangents into
+    those of ``y0``, ``a1`` and ``b1`` (xde_sde_srk_stage1_backward)."""
+
+    @staticmethod
+    def forward(ctx, backend, dt, s, seed, k, y0, a1, b1):
+        outs = tuple(torch.empty_like(y0) for _ in range(3))
+        backend._sde_srk_stage1(*outs, y0.detach(), a1.detach(), b1.detach(), dt, s, seed, k)
+        ctx.backend, ctx.meta = backend, (float(dt), float(s), int(seed), int(k))
+        return outs
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *gs):
+        gs = [_cotangent(g) for g in gs]
+        return (None,) * 5 + _sde_group_backward(ctx.backend._sde_srk_stage1_backward, gs, ctx.needs_input_grad[5:8],
+                                                 ((0, 1), (1, 2), (2, 3)), ctx.meta)
+
+
+class SdeSrkStage2Fn(torch.autograd.Function):
+    """SRK's last stage input ``G4`` (``HipBackend._sde_srk_stage2``) as an autograd node: backward is one launch writing the cotangents
+    of ``a1`` and of ``b1, b2, b3`` (xde_sde_srk_stage2_backward); ``gy0 = gG4`` needs no launch."""
+
+    @staticmethod
+    def forward(ctx, backend, dt, s, y0, a1, b1, b2, b3):
+        out = torch.empty_like(y0)
+        backend._sde_srk_stage2(out, y0.detach(), a1.detach(), b1.detach(), b2.detach(), b3.detach(), dt, s)
+        ctx.backend, ctx.meta = backend, (float(dt), float(s))
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        g = _cotangent(g)
+        rest = _sde_group_backward(ctx.backend._sde_srk_stage2_backward, [g], ctx.needs_input_grad[4:8], ((0, 1), (1, 4)), ctx.meta)
+        return (None,) * 3 + (g if ctx.needs_input_grad[3] else None,) + rest
+
+
+class SdeSrkStepFn(torch.autograd.Function):
+    """One SRK step (``HipBackend._sde_srk_step``) as an autograd node.  The node keeps only ``(dt, s, c, c3, seed, k)``: backward
+    regenerates Z and V in the launch that writes the cotangents of ``a1, a2`` and of ``b1 .. b4`` (xde_sde_srk_step_backward);
+    ``gy0 = gy1`` needs no launch."""
+
+    @staticmethod
+    def forward(ctx, backend, dt, s, c, c3, seed, k, y0, a1, a2, b1, b2, b3, b4):
+        out = torch.empty_like(y0)
+        backend._sde_srk_step(out, y0.detach(), a1.detach(), a2.detach(), b1.detach(), b2.detach(), b3.detach(), b4.detach(), dt, s, c,
+                              c3, seed, k)
+        ctx.backend, ctx.meta = backend, (float(dt), float(s), float(c), float(c3), int(seed), int(k))
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        g = _cotangent(g)
+        rest = _sde_group_backward(ctx.backend._sde_srk_step_backward, [g], ctx.needs_input_grad[8:14], ((0, 2), (2, 6)), ctx.meta)
+        return (None,) * 7 + (g if ctx.needs_input_grad[7] else None,) + rest

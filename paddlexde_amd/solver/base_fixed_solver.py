@@ -21,7 +21,7 @@ from ..xde.base_dde import DDE_DAMPING, BaseDDE
 from ..xde.base_ode import BaseODE
 from ..xde.base_sde import BaseSDE
 from ..xde.base_xde import BaseXDE
-from ._autograd import CombineFn, InterpRowsFn, SdeEulerFn, SdeMilsteinFn, SdeSupportFn
+from ._autograd import CombineFn, InterpRowsFn, SdeEulerFn, SdeMilsteinFn, SdeSrkStage1Fn, SdeSrkStage2Fn, SdeSrkStepFn, SdeSupportFn
 from ._common import as_operand, np_dtype, storage_ptr, t_span_to_host, upload
 
 _one_third = 1 / 3
@@ -114,7 +114,7 @@ class _SubSteps:
 class FixedSolver(metaclass=abc.ABCMeta):
     order: int
 
-    steps_sde = False  # the step is a convergent scheme for Ito SDEs (a BaseSDE problem): Euler, as Euler-Maruyama, and Milstein
+    steps_sde = False  # the step is a convergent scheme for Ito SDEs (a BaseSDE problem): Euler, as Euler-Maruyama, Milstein and SRK
 
     graphable = True  # the step's control flow does not depend on data (False: AdamsBashforthMoulton)
     GRAPH_MIN_STEPS = 4
@@ -165,13 +165,13 @@ class FixedSolver(metaclass=abc.ABCMeta):
             raise NotImplementedError("pipeline='graph' replays a captured step and cannot call xde.on_integrate_step_end; "
                                       "use pipeline='sync' (or the default 'auto', which then keeps the eager loop)")
         # the wrapper's fuse is what xde_stage_combine computes: BaseODE's `dy*dt + y0` or BaseDDE's damped form; BaseSDE's
-        # Euler-Maruyama update is xde_sde_em_step (Milstein adds its correction to it: xde_sde_milstein_step)
+        # Euler-Maruyama update is xde_sde_em_step (Milstein adds its correction to it: xde_sde_milstein_step; SRK is xde_sde_srk_*)
         fuse_impl = getattr(type(xde), "fuse", None)
         self._sde = fuse_impl is BaseSDE.fuse
         if self._sde:
             if not self.steps_sde:
                 raise NotImplementedError("{} does not step SDEs: its tableau does not converge for Ito SDEs; use Euler "
-                                          "(Euler-Maruyama) or Milstein".format(type(self).__name__))
+                                          "(Euler-Maruyama) or Milstein or SRK".format(type(self).__name__))
             if pipeline == "graph":
                 raise NotImplementedError("pipeline='graph' replays one captured step, which cannot advance the SDE's grid-step "
                                           "counter; use pipeline='sync' (or the default 'auto', which keeps the eager loop for SDEs)")
@@ -239,24 +239,26 @@ class FixedSolver(metaclass=abc.ABCMeta):
         return out if emit is None else (out, part)
 
     def _sde_prologue(self, t0, dtt, y0, dt):
-        """What both SDE steps start from: drift and diffusion at ``(t0, y0)`` as operands, ``dt``, ``s = sqrt(|dt|)`` and
-        ``c = 0.5/sqrt(|dt|)`` (0 for a zero-length step) computed in float64 and rounded to the state dtype, the grid step ``k``, and
-        whether an operand is being differentiated.  Returns ``(f, g, dt, s, c, k, grad)``, the scalars as Python floats."""
+        """What every SDE step starts from: drift and diffusion at ``(t0, y0)`` as operands, ``dt``, ``s = sqrt(|dt|)``,
+        ``c = 0.5/sqrt(|dt|)`` and ``c3 = 1/(6|dt|)`` (both 0 for a zero-length step) computed in float64 and rounded to the state dtype,
+        the grid step ``k``, and whether an operand is being differentiated.  Returns ``(f, g, dt, s, c, c3, k, grad)``, the scalars as
+        Python floats."""
         self.nfe += 1
         f, g = self.move(t0, dtt, y0)
         f, g = as_operand(f, like=y0), as_operand(g, like=y0)
         T = np_dtype(y0.dtype)
         root = np.sqrt(abs(np.float64(dt)))
         c = T(0.5 / root) if root > 0 else T(0.0)
+        c3 = T(1.0 / (6.0 * abs(np.float64(dt)))) if root > 0 else T(0.0)
         k = self._k if self._k is not None else 0  # (a step() call outside integrate() is the first step of a walk)
         grad = torch.is_grad_enabled() and (y0.requires_grad or f.requires_grad or g.requires_grad)
-        return f, g, float(dt), float(T(root)), float(c), k, grad
+        return f, g, float(dt), float(T(root)), float(c), float(c3), k, grad
 
     def _em_step(self, t0, dtt, y0, dt):
         """One Ito Euler-Maruyama step of a BaseSDE: ``y1 = (y0 + f*dt) + g*(s*Z)``, ``s = sqrt(|dt|)`` in the state dtype, Z the
         normals of (xde.seed, grid step k) — one xde_sde_em_step launch (SdeEulerFn when an operand is differentiated).  Returns
         ``(y1, f)``."""
-        f, g, dt, s, _, k, grad = self._sde_prologue(t0, dtt, y0, dt)
+        f, g, dt, s, _, _, k, grad = self._sde_prologue(t0, dtt, y0, dt)
         if grad:
             return SdeEulerFn.apply(self.backend, dt, s, self.xde.seed, k, y0, f, g), f
         out = self._y1_out if self._y1_out is not None else torch.empty_like(y0)
@@ -271,7 +273,7 @@ class FixedSolver(metaclass=abc.ABCMeta):
         step (which then returns y0), Z the normals of (xde.seed, grid step k) as in ``_em_step``.  Through SdeSupportFn /
         SdeMilsteinFn when an operand is differentiated.  ``nfe`` counts steps, as Euler's does: one per step, which here stands for
         one drift and two diffusion evaluations.  Returns ``(y1, f)``."""
-        f, g, dt, s, c, k, grad = self._sde_prologue(t0, dtt, y0, dt)
+        f, g, dt, s, c, _, k, grad = self._sde_prologue(t0, dtt, y0, dt)
         if grad:
             yb = SdeSupportFn.apply(self.backend, dt, s, y0, f, g)
             gb = as_operand(self.xde.diffusion(t0, yb), like=y0)
@@ -282,6 +284,33 @@ class FixedSolver(metaclass=abc.ABCMeta):
         out = self._y1_out if self._y1_out is not None else torch.empty_like(y0)
         self.backend._sde_milstein_step(out, y0, f, g, gb, dt, s, c, self.xde.seed, k)
         return out, f
+
+    def _srk_step(self, t0, t1, dtt, t34, t14, y0, dt):
+        """One SRK step of a BaseSDE (Roessler's SRI1W1: derivative-free, strong order 1.5, Ito, diagonal noise), three launches
+        around the evaluations they feed (the formulas in their written op order: include/xde_hip_sde.h) —
+        stage 1 writes ``Y2, G2, G3`` from ``a1 = drift(t0, y0)``, ``b1 = diffusion(t0, y0)``; then ``a2 = drift(t0 + 3/4 dt, Y2)``,
+        ``b2 = diffusion(t0 + 1/4 dt, G2)``, ``b3 = diffusion(t1, G3)``; stage 2 writes ``G4``; ``b4 = diffusion(t0 + 1/4 dt, G4)``; the
+        step writes ``y1``.  Stage 1 and the step draw Z and V of (xde.seed, grid step k) in registers; ``s``, ``c`` and ``c3`` as in
+        ``_sde_prologue``, ``c = c3 = 0`` for a zero-length step (which then returns y0).  Through SdeSrkStage1Fn / SdeSrkStage2Fn /
+        SdeSrkStepFn when an operand is differentiated.  ``nfe`` counts steps, as Euler's does: one per step, which here stands for 2
+        drift and 4 diffusion evaluations.  Returns ``(y1, a1)``."""
+        a1, b1, dt, s, c, c3, k, grad = self._sde_prologue(t0, dtt, y0, dt)
+        xde, seed = self.xde, self.xde.seed
+        drift = lambda t, y: as_operand(xde.call_func(t, y), like=y0)  # noqa: E731
+        diffusion = lambda t, y: as_operand(xde.diffusion(t, y), like=y0)  # noqa: E731
+        if grad:
+            Y2, G2, G3 = SdeSrkStage1Fn.apply(self.backend, dt, s, seed, k, y0, a1, b1)
+            a2, b2, b3 = drift(t34, Y2), diffusion(t14, G2), diffusion(t1, G3)
+            b4 = diffusion(t14, SdeSrkStage2Fn.apply(self.backend, dt, s, y0, a1, b1, b2, b3))
+            return SdeSrkStepFn.apply(self.backend, dt, s, c, c3, seed, k, y0, a1, a2, b1, b2, b3, b4), a1
+        Y2, G2, G3, G4 = (torch.empty_like(y0) for _ in range(4))
+        self.backend._sde_srk_stage1(Y2, G2, G3, y0, a1, b1, dt, s, seed, k)
+        a2, b2, b3 = drift(t34, Y2), diffusion(t14, G2), diffusion(t1, G3)
+        self.backend._sde_srk_stage2(G4, y0, a1, b1, b2, b3, dt, s)
+        b4 = diffusion(t14, G4)
+        out = self._y1_out if self._y1_out is not None else torch.empty_like(y0)
+        self.backend._sde_srk_step(out, y0, a1, a2, b1, b2, b3, b4, dt, s, c, c3, seed, k)
+        return out, a1
 
     def _combine_pre(self, y0, pre, ks, coef, dt, scale, out=None):
         """The final weighted sum with its leading terms pre-summed (xde_stage_combine_pre_weighted): reads y0, ``pre`` and the newest

@@ -4,7 +4,7 @@
 and dtype that multiplies the Brownian increment element by element.  ``move`` evaluates both coefficients and ``fuse`` is the Ito
 Euler-Maruyama update ``(y0 + f*dt) + g*dW``, the step the reference meant (its ``move`` computes ``f(t0, y0)`` and
 ``g(t0, y0) * I_k`` with ``I_k = bm(t0, t1)``; its ``fuse`` is marked TODO).  The fixed-step solvers never call ``fuse``: they map a
-``BaseSDE`` onto xde_sde_em_step (Euler) or xde_sde_milstein_step (Milstein), which form ``dW = sqrt(|dt|) * Z`` from a counter-based generator inside the kernel (no Brownian
+``BaseSDE`` onto xde_sde_em_step (Euler), xde_sde_milstein_step (Milstein) or xde_sde_srk_step (SRK), which form ``dW = sqrt(|dt|) * Z`` from a counter-based generator inside the kernel (no Brownian
 object: the noise of element e at grid step k is a function of (seed, k, e) — include/xde_hip_sde.h).
 """
 import numpy as np
@@ -48,7 +48,7 @@ class BaseSDE(BaseXDE):
         pass
 
     def diffusion(self, t, y):
-        """``g(t, y)``, checked: a tensor of y's shape and dtype (diagonal noise).  Milstein's support evaluation calls it too."""
+        """``g(t, y)``, checked: a tensor of y's shape and dtype (diagonal noise).  Milstein's support evaluation and SRK's stage evaluations call it too."""
         g = self.g(t, y)
         if not torch.is_tensor(g) or g.shape != y.shape or g.dtype != y.dtype:
             got = "{} {}".format(tuple(g.shape), g.dtype) if torch.is_tensor(g) else type(g).__name__
