@@ -21,6 +21,13 @@ def _np(t):
     return t.detach().numpy()
 
 
+def _fmax(a, b):
+    """The kernels' fmax_ (v_max_f32 / v_max_f64): a NaN of EITHER kind counts as missing.  (np.fmax agrees in its vector loops, but its
+    scalar remainder loop hands the pair to libm's fmax, which returns NaN for a signalling NaN: the result would depend on where in
+    the array the element sits.)"""
+    return np.where(np.isnan(a), b, np.where(np.isnan(b), a, np.maximum(a, b)))
+
+
 class NumpyDoubleBackend:
     name = "numpy-double(test)"
 
@@ -176,7 +183,7 @@ class NumpyDoubleBackend:
             e = kk[0] * cs[0] if e_pre is None else _np(e_pre).reshape(-1) + kk[0] * cs[0]
             for j in range(1, len(kk)):
                 e = e + kk[j] * cs[j]
-            tol = T(atol) + T(rtol) * np.fmax(np.abs(y0v), np.abs(y1v))
+            tol = T(atol) + T(rtol) * _fmax(np.abs(y0v), np.abs(y1v))
             r = e / tol
         self._slots[0] = self._seg_reduce(r, y0v, segs, norm_kind) + (norm_kind, segs.n_seg)
 
@@ -204,7 +211,7 @@ class NumpyDoubleBackend:
             e = kk[0] * cs[0]
             for j in range(1, len(kk)):
                 e = e + kk[j] * cs[j]
-            _np(out).reshape(-1)[...] = e / (T(atol) + T(rtol) * np.fmax(np.abs(y0v), np.abs(y1v)))
+            _np(out).reshape(-1)[...] = e / (T(atol) + T(rtol) * _fmax(np.abs(y0v), np.abs(y1v)))
         if nonfinite_out is not None:
             nonfinite_out += float(np.count_nonzero(~np.isfinite(y0v)))
 

@@ -371,3 +371,96 @@ def test_step_callbacks_adaptive_and_fixed(dev):
         assert t0 == float(tf[i]) and t1 == float(tf[i + 1]) and torch.equal(a, out[i : i + 1]) and torch.equal(b, out[i + 1 : i + 2])
     with pytest.raises(NotImplementedError, match="on_integrate_step_end"):
         RK4(xde=xw, y0=ys, rtol=1e-7, atol=1e-9, norm=P_rms(), pipeline="graph")
+
+
+# ----------------------------------------------------------------------------------------------
+# +-Inf in the state: the error norm's non-finite count is the ONLY guard (tol = atol + rtol * inf = inf, e / inf = 0: the ratio
+# stays finite, where a NaN makes it NaN and trips "underflow in dt" as well).  A kernel that loses the count returns an infinite
+# solution instead of raising the reference's `assert isfinite(y0).all()` (base_adaptive_solver_rk.py:201).
+# ----------------------------------------------------------------------------------------------
+_NF_MESSAGE = r"non-finite values in state `y`: 1 non-finite element\(s\)"
+_NF_DT = {"f32": torch.float32, "f64": torch.float64}
+
+
+def _nf_sizes(dtype):
+    """8 elements: the one-workgroup error-norm + controller launch.  W (512 * 256 + 37) + (W - 1): the FSAL pair's pipelined
+    error-norm kernel at the smallest size where one wave leaves its loop at two trip counts (W elements per 16-byte load,
+    workgroups of 256 lanes, a norm grid of 512), with a ragged last wave and a full scalar tail."""
+    w = 4 if dtype == "f32" else 2
+    n = w * (512 * 256 + 37) + (w - 1)
+    return {"small": (8, {"first": 0, "last": 7}), "large": (n, {"first": 0, "ragged": w * (n // w - 1), "tail": n - 1})}
+
+
+def _nf_values(n, dtype):
+    """Multiples of 1/4 up to 1.5: the interpolant's integer multiples of the state (18 y0 + 14 y1 - 32 y_mid, ...) are exact, so a
+    zero derivative returns y0 to the BIT at every output time, whatever the step sequence."""
+    return ((torch.arange(n) % 13) - 6).to(_NF_DT[dtype]) * 0.25
+
+
+def _nf_solve(dev, solver, dtype, pipeline, n, plant=None, value=None):
+    y0 = _nf_values(n, dtype)
+    if plant is not None:
+        y0[plant] = value
+    y0 = y0.to(dev)
+    t = torch.tensor([0.0, 0.4, 1.0], dtype=_NF_DT[dtype])
+    sol = odeint(lambda t_, y: torch.zeros_like(y), y0, t, solver=solver, rtol=1e-5, atol=1e-7,
+                 options={"norm": _rms_norm, "first_step": 0.1, "pipeline": pipeline})
+    return y0, sol
+
+
+_NF_CASES = ([(Dopri5, size, where) for size, wheres in (("small", ("first", "last")), ("large", ("first", "ragged", "tail"))) for where in wheres])
+
+
+@pytest.mark.parametrize("solver,size,where", _NF_CASES, ids=lambda v: getattr(v, "__name__", v))
+@pytest.mark.parametrize("pipeline", ["sync", "lag"])
+@pytest.mark.parametrize("dtype", ["f32", "f64"])
+def test_one_infinity_in_the_state_raises_the_reference_assertion(dev, dtype, pipeline, solver, size, where):
+    n, spots = _nf_sizes(dtype)[size]
+    value = float("inf") if (spots[where] + (pipeline == "lag")) % 2 == 0 else -float("inf")
+    with pytest.raises(AssertionError, match=_NF_MESSAGE):
+        _nf_solve(dev, solver, dtype, pipeline, n, spots[where], value)
+
+
+@pytest.mark.parametrize("solver,dtype,pipeline,where,value", [(Dopri8, "f32", "sync", "ragged", float("inf")), (Dopri8, "f64", "lag", "tail", -float("inf")),
+                                                               (Bosh3, "f64", "lag", "tail", float("inf")), (Bosh3, "f32", "sync", "first", -float("inf"))],
+                         ids=lambda v: getattr(v, "__name__", str(v)))
+def test_one_infinity_in_the_state_raises_with_other_tableaus(dev, solver, dtype, pipeline, where, value):
+    """Dopri8's error estimate reads 11 derivatives (the wide error-norm kernel); Bosh3 is the other FSAL pair."""
+    n, spots = _nf_sizes(dtype)["large"]
+    with pytest.raises(AssertionError, match=_NF_MESSAGE):
+        _nf_solve(dev, solver, dtype, pipeline, n, spots[where], value)
+
+
+@pytest.mark.parametrize("solver,size", [(Dopri5, "small"), (Dopri5, "large"), (Dopri8, "large"), (Bosh3, "large")], ids=lambda v: getattr(v, "__name__", v))
+@pytest.mark.parametrize("pipeline", ["sync", "lag"])
+@pytest.mark.parametrize("dtype", ["f32", "f64"])
+def test_the_same_calls_with_a_finite_state_return_the_constant_solution(dev, dtype, pipeline, solver, size):
+    """Control of the cases above: nothing but the planted element makes them raise."""
+    n, _ = _nf_sizes(dtype)[size]
+    y0, sol = _nf_solve(dev, solver, dtype, pipeline, n)
+    assert tuple(sol.shape) == (3, n) and all(torch.equal(row, y0) for row in sol)
+
+
+@pytest.mark.parametrize("pipeline", ["sync", "lag"])
+@pytest.mark.parametrize("dtype", ["f32", "f64"])
+def test_one_infinity_in_the_last_member_of_an_18_member_tuple_state(dev, dtype, pipeline):
+    """A tuple state with more than XDE_MAX_SEG = 16 members under the per-member norm (max over members of the RMS: the shape of
+    odeint_adjoint's default norm, the only native norm with one segment per member) is reduced in chunks of 16 segments
+    (`_reduce_chunks`): the count of the SECOND chunk — members 16 and 17 — must arrive at the controller with the first one's."""
+    from paddlexde_amd.functional.odeint_adjoint import SegmentMaxNorm
+
+    assert _hip.XDE_MAX_SEG == 16
+    members = [_nf_values(1 + (3 * i) % 7, dtype).reshape(-1, 1) for i in range(18)]
+    t = torch.tensor([0.0, 0.4, 1.0], dtype=_NF_DT[dtype])
+
+    def solve(ys):
+        return odeint(lambda t_, y: tuple(torch.zeros_like(x) for x in y), tuple(x.to(dev) for x in ys), t, solver=Dopri5, rtol=1e-5, atol=1e-7,
+                      options={"norm": SegmentMaxNorm(_rms_norm, None), "first_step": 0.1, "pipeline": pipeline})
+
+    sol = solve(members)
+    assert len(sol) == 18 and all(torch.equal(row.cpu(), m) for s, m in zip(sol, members) for row in s)
+    for value in (float("inf"), -float("inf")):
+        bad = [m.clone() for m in members]
+        bad[17][-1, 0] = value
+        with pytest.raises(AssertionError, match=_NF_MESSAGE):
+            solve(bad)

@@ -346,6 +346,29 @@ def test_direct_rccl_exchange_is_not_offered_to_the_graph_pipeline(cpu_double):
 # ----------------------------------------------------------------------------------------------
 # one-shot peer-to-peer norm exchange (utils.PeerExchange / xde_p2p_*): rehearsal with two processes on ONE GPU
 # ----------------------------------------------------------------------------------------------
+def _one_infinity_message(rank, world, norm_name, pipeline, exchange):
+    """dy/dt = 0 on 64 x 8 rows per rank, ONE +inf in the last rank's rows only: what the solve raises on this rank.  tol = atol +
+    rtol * inf = inf and e / inf = 0, so every rank's error ratio is finite: only the non-finite count, carried from the last rank to
+    all of them by the exchange, stops the solve.  (Without it the other ranks would walk on alone and the exchange would give up
+    at its spin limit with an XdeError — which is not caught here.)"""
+    from paddlexde_amd import Dopri5
+    from paddlexde_amd.utils import _linf_norm, _rms_norm
+    from paddlexde_amd.xde import BaseODE
+
+    y0 = (((torch.arange(64 * 8) % 13) - 6).float() * 0.25).reshape(64, 8)
+    if rank == world - 1:
+        y0[61, 3] = float("inf")
+    y0 = y0.to("cuda:0")
+    t = torch.tensor([0.0, 0.4, 1.0])
+    s = Dopri5(xde=BaseODE(lambda t_, y: torch.zeros_like(y), y0=y0, t_span=t), y0=y0, rtol=1e-5, atol=1e-7,
+               norm=_rms_norm if norm_name == "rms" else _linf_norm, process_group=True, pipeline=pipeline, norm_exchange=exchange, first_step=0.1)
+    try:
+        s.integrate(t)
+    except AssertionError as e:
+        return str(e)
+    return "the solve returned"
+
+
 def _p2p_worker(rank, world, port, out_dir, norm_name, pipeline):
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
@@ -380,11 +403,18 @@ def _p2p_worker(rank, world, port, out_dir, norm_name, pipeline):
             ex.fused_control = True
             # the all-reduce twin (gloo): a captured step cannot hold it, so the graph case is compared with the lag pipeline
             sol2, s2 = _solve(y0[rows].contiguous().to("cuda:0"), A.to("cuda:0"), True, norm_name, "lag" if pipeline == "graph" else pipeline)
+            # the non-finite count of ONE rank's rows crosses the exchange: the one launch, then the three it replaces
+            nf_msgs = []
+            for fused in (True, False):
+                ex.fused_control = fused
+                nf_msgs.append(_one_infinity_message(rank, world, norm_name, pipeline, ex))
+            ex.fused_control = True
+            assert ex.error() == 0
         finally:
             ex.close()
         tr = lambda so: np.asarray([[a, b, c, float(d)] for a, b, c, d in so.trace])  # noqa: E731
         np.savez(os.path.join(out_dir, "p2p{}.npz".format(rank)), sol=sol.cpu().numpy(), trace=tr(s), sol_ar=sol2.cpu().numpy(),
-                 trace_ar=tr(s2), sol_3=sol3.cpu().numpy(), trace_3=tr(s3))
+                 trace_ar=tr(s2), sol_3=sol3.cpu().numpy(), trace_3=tr(s3), nf_msgs=np.asarray(nf_msgs))
     finally:
         dist.destroy_process_group()
 
@@ -414,6 +444,11 @@ def test_peer_exchange_two_ranks_on_one_gpu(tmp_path, norm_name, pipeline, world
             assert np.allclose(r["trace"][:, :3], r["trace_ar"][:, :3], rtol=1e-6, atol=1e-12)
             assert P.rel_err(r["sol"], r["sol_ar"]) <= 1e-6
     assert len(rs[0]["trace"]) > 5
+    # one +inf in the last rank's rows: EVERY rank raised the reference's assertion, with the one count, fused and unfused
+    for r in rs:
+        assert list(r["nf_msgs"]) == list(rs[0]["nf_msgs"]) and len(r["nf_msgs"]) == 2
+        for m in r["nf_msgs"]:
+            assert "non-finite values in state" in str(m) and "1 non-finite element" in str(m), str(m)
 
 
 def _p2p_timeout_worker(rank, world, port, out_dir):
