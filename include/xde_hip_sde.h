@@ -1,6 +1,6 @@
 /*
- * xde_hip_sde.h — entry points of libxde_hip.so for sdeint: Ito Euler-Maruyama, Milstein and SRK steps with diagonal noise whose Brownian
- * increments are generated inside the kernel (host side: paddlexde_amd/solver/base_fixed_solver.py, paddlexde_amd/functional/sdeint.py).
+ * xde_hip_sde.h — entry points of libxde_hip.so for sdeint: Ito Euler-Maruyama, Milstein and SRK steps and Stratonovich reversible Heun
+ * steps (with the cotangent sweep of sdeint_adjoint) with diagonal noise whose Brownian increments are generated inside the kernel (host side: paddlexde_amd/solver/base_fixed_solver.py, paddlexde_amd/functional/sdeint.py).
  *
  * Same conventions as xde_hip.h (status codes, device pointers borrowed from the caller, `stream` = hipStream_t as void*,
  * XDE_F32 / XDE_F64).  Arguments are validated on the host before anything is enqueued.
@@ -128,6 +128,48 @@ int xde_sde_srk_stage2_backward(void* ga1, void* gb1, void* gb2, void* gb3, cons
  *   ga1 = gy1 * (1/3 * dt),  ga2 = gy1 * (2/3 * dt),  gb_i = gy1 * e_i */
 int xde_sde_srk_step_backward(void* ga1, void* ga2, void* gb1, void* gb2, void* gb3, void* gb4, const void* gy1, int64_t n, double dt,
                               double s, double c, double c3, uint64_t seed, int64_t k, int dtype, void* stream);
+
+/*
+ * REVERSIBLE HEUN (Kidger, Foster, Li, Lyons, "Efficient and Accurate Gradients for Neural SDEs", NeurIPS 2021: algebraically
+ * reversible, Stratonovich, diagonal noise, one drift and one diffusion evaluation per step; strong order 1 where g_i depends on y_i
+ * only).  The one Stratonovich scheme of this header: every entry point above is Ito.  The carried state is (y, yh, fh, gh) with
+ * yh = y0, fh = drift(t0, y0), gh = diffusion(t0, y0) at the first grid step.  Z is the Z of (seed, k) above and w = s * Z; where
+ * s == 0 the generator is skipped and w = s (a zero-length step: y1 = y0 exactly, yh1 = 2 y0 - yh0).  `direction` is +1 or -1
+ * (anything else: XDE_EBADARG, checked first): dt and s are multiplied by it, exactly, before the formulas — the reverse step is the
+ * forward step's two formulas at direction -1, applied to the state at t1.
+ *
+ * Predict, one launch, 5 n elements moved; yh1 may be yh0, no other overlap:
+ *   yh1 = (((y0 + y0) - yh0) + f0 * dt) + g0 * w
+ * The caller then evaluates f1 = drift(t1, yh1), g1 = diffusion(t1, yh1). */
+int xde_sde_rheun_predict(void* yh1, const void* y0, const void* yh0, const void* f0, const void* g0, int64_t n, double dt, double s,
+                          int direction, uint64_t seed, int64_t k, int dtype, void* stream);
+
+/* Correct, one launch, 6 n; y1 may be y0, no other overlap:
+ *   y1 = (y0 + (f0 + f1) * (0.5 * dt)) + (g0 + g1) * (0.5 * w)
+ * The cotangents of predict and correct need no entry point of their own: xde_sde_em_backward at (dt, s) writes predict's gf0, gg0
+ * (gy0 = gyh1 + gyh1, gyh0 = -gyh1), and at (0.5 * dt, 0.5 * s) correct's gf0 = gf1, gg0 = gg1 (gy0 = gy1), bit for bit: halving is
+ * exact. */
+int xde_sde_rheun_correct(void* y1, const void* y0, const void* f0, const void* f1, const void* g0, const void* g1, int64_t n, double dt,
+                          double s, int direction, uint64_t seed, int64_t k, int dtype, void* stream);
+
+/* THE COTANGENT SWEEP of the reversible Heun scheme (state cotangents ay, ayh, af, ag; dt, s and w the forward step's), two launches
+ * per backward step around the vjp they feed.
+ *
+ * Stage, 5 n (3 n on the first backward step):
+ *   bf = af1 + ay1 * (0.5 * dt)        bg = ag1 + ay1 * (0.5 * w)
+ * af1 and ag1 may be null together and are then read as zero (the first backward step: bf = ay1 * (0.5 * dt),
+ * bg = ay1 * (0.5 * w)); one of them null is refused.  bf may be af1 and bg may be ag1; no other overlap.  The caller then takes
+ * v = the vjp of (f1, g1) at yh1 with (bf, bg). */
+int xde_sde_rheun_adjoint_stage(void* bf, void* bg, const void* af1, const void* ag1, const void* ay1, int64_t n, double dt, double s,
+                                uint64_t seed, int64_t k, int dtype, void* stream);
+
+/* Step, one launch, 7 n (6 n on the first backward step):
+ *   A    = ayh1 + v
+ *   ay0  = ay1 + (A + A)                      ayh0 = -A
+ *   af0  = ay1 * (0.5 * dt) + A * dt          ag0  = ay1 * (0.5 * w) + A * w
+ * ayh1 may be null and is then read as zero (A = v).  ay0 may be ay1 and ayh0 may be ayh1; no other overlap. */
+int xde_sde_rheun_adjoint_step(void* ay0, void* ayh0, void* af0, void* ag0, const void* ay1, const void* ayh1, const void* v, int64_t n,
+                               double dt, double s, uint64_t seed, int64_t k, int dtype, void* stream);
 
 /* The generator itself (tests, diagnostics): mode XDE_NOISE_NORMAL writes the Z the step kernels above use (the same device
  * function); XDE_NOISE_BITS writes Philox words (dtype is checked but does not change them). */

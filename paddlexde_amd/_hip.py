@@ -182,7 +182,7 @@ BACKPROP_PROTOTYPES = {
 GRID_PROTOTYPES = {
     "xde_interp_rows": (_i32, [_vpp, C.POINTER(C.c_int), _dp, _i32, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i64, _i32, _vp]),
 }
-# the entry points of include/xde_hip_sde.h (sdeint's Euler-Maruyama, Milstein and SRK steps); bound by load_library() after _bind
+# the entry points of include/xde_hip_sde.h (sdeint's Euler-Maruyama, Milstein, SRK and reversible Heun steps); bound by load_library() after _bind
 SDE_PROTOTYPES = {
     "xde_sde_em_step": (_i32, [_vp, _vp, _vp, _vp, _i64, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
     "xde_sde_em_backward": (_i32, [_vp, _vp, _vp, _i64, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
@@ -198,6 +198,10 @@ SDE_PROTOTYPES = {
     "xde_sde_srk_stage2_backward": (_i32, [_vp] * 5 + [_i64, _dbl, _dbl, _i32, _vp]),
     "xde_sde_srk_step_backward": (_i32, [_vp] * 7 + [_i64, _dbl, _dbl, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
     "xde_sde_noise_draw": (_i32, [_vp, _i64, C.c_uint64, _i64, _i32, _i32, _i32, _vp]),
+    "xde_sde_rheun_predict": (_i32, [_vp] * 5 + [_i64, _dbl, _dbl, _i32, C.c_uint64, _i64, _i32, _vp]),
+    "xde_sde_rheun_correct": (_i32, [_vp] * 6 + [_i64, _dbl, _dbl, _i32, C.c_uint64, _i64, _i32, _vp]),
+    "xde_sde_rheun_adjoint_stage": (_i32, [_vp] * 5 + [_i64, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
+    "xde_sde_rheun_adjoint_step": (_i32, [_vp] * 7 + [_i64, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
 }
 SYMBOLS = tuple(PROTOTYPES)
 BACKPROP_SYMBOLS = tuple(BACKPROP_PROTOTYPES)
@@ -793,9 +797,10 @@ class HipBackend:
     # solvers' SDE path (and its autograd node) call these.
     def _sde_call(self, who, outs, ins, *scalars):
         """One launch of the step entry point ``xde<who>(*outs, *ins, n, *scalars, dtype, stream)``: contiguous tensors of one shape and
-        dtype on the device; an output given as None goes in as a null pointer (a skipped output of a backward)."""
+        dtype on the device; an output given as None goes in as a null pointer (a skipped output of a backward), and so does an input
+        (the zero cotangents of the reversible Heun sweep's first backward step)."""
         self._require_device(*outs, *ins)
-        like = ins[0]
+        like = next(x for x in ins if x is not None)
         for x in (*ins, *outs):
             if x is not None and (not x.is_contiguous() or x.shape != like.shape or x.dtype != like.dtype):
                 raise XdeError("{}: the operands must be contiguous tensors of one shape and dtype".format(who))
@@ -857,6 +862,27 @@ class HipBackend:
         be None: skipped), one launch regenerating the forward's draws."""
         self._sde_call("_sde_srk_step_backward", (ga1, ga2, gb1, gb2, gb3, gb4), (gy1,), float(dt), float(s), float(c), float(c3),
                        int(seed), int(k))
+
+    def _sde_rheun_predict(self, yh1, y0, yh0, f0, g0, dt, s, direction, seed, k):
+        """Reversible Heun's prediction ``yh1 = (((y0 + y0) - yh0) + f0*dt) + g0*w``, ``w = s*Z`` with Z the normals of (``seed``, step
+        ``k``), ``dt`` and ``w`` times ``direction`` (+1, or -1: the reverse step); ``yh1`` may be ``yh0``.  One launch."""
+        self._sde_call("_sde_rheun_predict", (yh1,), (y0, yh0, f0, g0), float(dt), float(s), int(direction), int(seed), int(k))
+
+    def _sde_rheun_correct(self, y1, y0, f0, f1, g0, g1, dt, s, direction, seed, k):
+        """Reversible Heun's correction ``y1 = (y0 + (f0 + f1)*(0.5*dt)) + (g0 + g1)*(0.5*w)``, ``dt`` and ``w`` times ``direction``;
+        ``y1`` may be ``y0``.  One launch."""
+        self._sde_call("_sde_rheun_correct", (y1,), (y0, f0, f1, g0, g1), float(dt), float(s), int(direction), int(seed), int(k))
+
+    def _sde_rheun_adjoint_stage(self, bf, bg, af1, ag1, ay1, dt, s, seed, k):
+        """The cotangents the sweep's vjp takes: ``bf = af1 + ay1*(0.5*dt)``, ``bg = ag1 + ay1*(0.5*w)``; ``af1`` and ``ag1`` None
+        together: zero (the first backward step).  ``bf`` may be ``af1`` and ``bg`` may be ``ag1``.  One launch regenerating Z."""
+        self._sde_call("_sde_rheun_adjoint_stage", (bf, bg), (af1, ag1, ay1), float(dt), float(s), int(seed), int(k))
+
+    def _sde_rheun_adjoint_step(self, ay0, ayh0, af0, ag0, ay1, ayh1, v, dt, s, seed, k):
+        """One backward step of the state cotangents: ``A = ayh1 + v``, ``ay0 = ay1 + (A + A)``, ``ayh0 = -A``,
+        ``af0 = ay1*(0.5*dt) + A*dt``, ``ag0 = ay1*(0.5*w) + A*w``; ``ayh1`` None: zero.  ``ay0`` may be ``ay1`` and ``ayh0`` may be
+        ``ayh1``.  One launch regenerating Z."""
+        self._sde_call("_sde_rheun_adjoint_step", (ay0, ayh0, af0, ag0), (ay1, ayh1, v), float(dt), float(s), int(seed), int(k))
 
     def _sde_noise(self, out, seed, k, bits=False, draw=0):
         """The generator's output for (``seed``, step ``k``) into the contiguous ``out``: the normals Z (``out``'s dtype), or with

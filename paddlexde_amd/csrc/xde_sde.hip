@@ -1,4 +1,4 @@
-// libxde_hip.so — Ito Euler-Maruyama, Milstein and SRK (strong order 1.5) steps with in-kernel Brownian increments (C ABI:
+// libxde_hip.so — Ito Euler-Maruyama, Milstein and SRK (strong order 1.5) steps and Stratonovich reversible Heun steps with in-kernel Brownian increments (C ABI:
 // include/xde_hip_sde.h; host: paddlexde_amd/solver/base_fixed_solver.py).
 //
 // One lane serves one Philox4x32-10 call per draw: 4 fp32 or 2 fp64 elements, i.e. exactly one 16-byte vector of every operand.  The
@@ -7,7 +7,7 @@
 // lane: Z from the counter's last word 0 (the draw of EM and Milstein) and V from last word 1.
 //
 // The file is three layers.  Each formula is written once, as a per-element functor (EmStep, EmBackward, MilsteinStep,
-// MilsteinBackward, SrkStage1, SrkStage2, SrkStep and their backwards); the Milstein support point is the EM functors with
+// MilsteinBackward, SrkStage1, SrkStage2, SrkStep and their backwards, RheunPredict, RheunCorrect, RheunAdjointStage, RheunAdjointStep); the Milstein support point is the EM functors with
 // NOISE = false (s in the place of s * Z, the generator compiled out).  One kernel, xde_sde_step_kernel, owns the lane loop for all of them: a lane whose block runs past n (the tail), or any launch
 // whose pointers are not all 16-byte aligned, takes the scalar path with the same bits; grid-stride over at most grid_cap() workgroups
 // of kBlock.  One host launcher, sde_launch, owns the argument checks, the profiling scope and the dtype x alignment x output-mask
@@ -244,6 +244,56 @@ struct SrkStepBackward {  // ga1 = gy1 * (1/3 * dt), ga2 = gy1 * (2/3 * dt), gb_
   }
 };
 
+// REVERSIBLE HEUN (Stratonovich, diagonal noise; include/xde_hip_sde.h).  The entry points hand dt and s over already multiplied by
+// the direction (+1 / -1: exact), and take the NOISE = false form (s in the place of s * Z, the generator compiled out) where s == 0.
+struct RheunPredict : OneDraw {  // yh1 = (((y0 + y0) - yh0) + f0 * dt) + g0 * w        x = y0, yh0, f0, g0
+  static constexpr int NI = 4, NO = 1, ZMASK = 1;
+  template <bool NOISE, typename T> __device__ static void apply(const T (&x)[NI], T z, const Coef<T>& k, T (&o)[NO]) {
+    const T w = NOISE ? k.s * z : k.s;
+    o[0] = (((x[0] + x[0]) - x[1]) + x[2] * k.dt) + x[3] * w;
+  }
+};
+
+struct RheunCorrect : OneDraw {  // y1 = (y0 + (f0 + f1) * (0.5 * dt)) + (g0 + g1) * (0.5 * w)        x = y0, f0, f1, g0, g1
+  static constexpr int NI = 5, NO = 1, ZMASK = 1;
+  template <bool NOISE, typename T> __device__ static void apply(const T (&x)[NI], T z, const Coef<T>& k, T (&o)[NO]) {
+    const T w = NOISE ? k.s * z : k.s;
+    o[0] = (x[0] + (x[1] + x[2]) * (T(0.5) * k.dt)) + (x[3] + x[4]) * (T(0.5) * w);
+  }
+};
+
+// the cotangent sweep's two launches; FIRST = the first backward step, whose af1, ag1 (stage) or ayh1 (step) are zero and not read
+template <bool FIRST> struct RheunAdjointStage {  // bf = af1 + ay1 * (0.5 * dt), bg = ag1 + ay1 * (0.5 * w)        x = ay1, af1, ag1
+  static constexpr int NI = FIRST ? 1 : 3, NO = 2, ZMASK = 2, DRAWS = 1;
+  static constexpr bool ok(int m) { return m == 3; }
+  template <bool NOISE, typename T> __device__ static void apply(const T (&x)[NI], T z, const Coef<T>& k, T (&o)[NO]) {
+    const T w = NOISE ? k.s * z : k.s;
+    const T hf = x[0] * (T(0.5) * k.dt), hg = x[0] * (T(0.5) * w);
+    if constexpr (FIRST) {
+      o[0] = hf;
+      o[1] = hg;
+    } else {
+      o[0] = x[1] + hf;
+      o[1] = x[2] + hg;
+    }
+  }
+};
+
+template <bool FIRST> struct RheunAdjointStep {  // A = ayh1 + v, ay0 = ay1 + (A + A), ayh0 = -A, af0 = ay1 * (0.5 * dt) + A * dt,
+                                                 // ag0 = ay1 * (0.5 * w) + A * w        x = ay1, v, ayh1
+  static constexpr int NI = FIRST ? 2 : 3, NO = 4, ZMASK = 8, DRAWS = 1;
+  static constexpr bool ok(int m) { return m == 15; }
+  template <bool NOISE, typename T> __device__ static void apply(const T (&x)[NI], T z, const Coef<T>& k, T (&o)[NO]) {
+    const T w = NOISE ? k.s * z : k.s;
+    T A = x[1];
+    if constexpr (!FIRST) A = x[2] + x[1];
+    o[0] = x[0] + (A + A);
+    o[1] = -A;
+    o[2] = x[0] * (T(0.5) * k.dt) + A * k.dt;
+    o[3] = x[0] * (T(0.5) * w) + A * w;
+  }
+};
+
 // one element of a formula: with both draws where it takes V
 template <bool NOISE, class Op, typename T>
 __device__ __forceinline__ void apply_op(const T (&x)[Op::NI], T z, T v, const Coef<T>& k, T (&o)[Op::NO]) {
@@ -444,6 +494,17 @@ int sde_launch(const char* who, int kid, bool backward, const char* cotangent, v
   return XDE_OK;
 }
 
+// The host side of the reversible Heun entry points: the direction first (+1 / -1; it multiplies dt and s, exactly), then sde_launch —
+// the form without the generator where s == 0 (w = s there: a zero-length step adds exact zeros).
+template <class Op>
+int rheun_launch(const char* who, int kid, void* const (&outs)[Op::NO], const void* const (&ins)[Op::NI], int64_t n, double dt, double s,
+                 int direction, uint64_t seed, int64_t k, int dtype, void* stream) {
+  if (direction != 1 && direction != -1) return fail(XDE_EBADARG, std::string(who) + ": direction must be +1 or -1");
+  const double d = direction;
+  if (s != 0.0) return sde_launch<Op>(who, kid, false, nullptr, outs, ins, n, d * dt, d * s, 0.0, 0.0, seed, k, dtype, stream);
+  return sde_launch<Op, false>(who, kid, false, nullptr, outs, ins, n, d * dt, d * s, 0.0, 0.0, seed, k, dtype, stream);
+}
+
 }  // namespace
 
 extern "C" {
@@ -523,6 +584,37 @@ int xde_sde_srk_step_backward(void* ga1, void* ga2, void* gb1, void* gb2, void* 
                               double s, double c, double c3, uint64_t seed, int64_t k, int dtype, void* stream) {
   return sde_launch<SrkStepBackward>("xde_sde_srk_step_backward", XDE_KID_COMBINE, true, "gy1", {ga1, ga2, gb1, gb2, gb3, gb4}, {gy1}, n,
                                      dt, s, c, c3, seed, k, dtype, stream);
+}
+
+// REVERSIBLE HEUN (Stratonovich, diagonal noise): predict, correct, and the cotangent sweep's stage and step.  dt and s go to the
+// kernel times the direction; a step with s == 0 takes no noise (rheun_launch: the generator is compiled out of that form).
+// (the prediction is a stage input: the stage combines' id)
+int xde_sde_rheun_predict(void* yh1, const void* y0, const void* yh0, const void* f0, const void* g0, int64_t n, double dt, double s,
+                          int direction, uint64_t seed, int64_t k, int dtype, void* stream) {
+  return rheun_launch<RheunPredict>("xde_sde_rheun_predict", XDE_KID_COMBINE, {yh1}, {y0, yh0, f0, g0}, n, dt, s, direction, seed, k, dtype, stream);
+}
+
+// (the SDE's fuse, as the EM step)
+int xde_sde_rheun_correct(void* y1, const void* y0, const void* f0, const void* f1, const void* g0, const void* g1, int64_t n, double dt,
+                          double s, int direction, uint64_t seed, int64_t k, int dtype, void* stream) {
+  return rheun_launch<RheunCorrect>("xde_sde_rheun_correct", XDE_KID_COMBINE_FUSE, {y1}, {y0, f0, f1, g0, g1}, n, dt, s, direction, seed, k, dtype,
+                                    stream);
+}
+
+// (af1 and ag1 null together: the first backward step, which does not read them; one of them null is refused with the null pointers)
+int xde_sde_rheun_adjoint_stage(void* bf, void* bg, const void* af1, const void* ag1, const void* ay1, int64_t n, double dt, double s,
+                                uint64_t seed, int64_t k, int dtype, void* stream) {
+  const char* who = "xde_sde_rheun_adjoint_stage";
+  if (!af1 && !ag1) return rheun_launch<RheunAdjointStage<true>>(who, XDE_KID_COMBINE, {bf, bg}, {ay1}, n, dt, s, 1, seed, k, dtype, stream);
+  return rheun_launch<RheunAdjointStage<false>>(who, XDE_KID_COMBINE, {bf, bg}, {ay1, af1, ag1}, n, dt, s, 1, seed, k, dtype, stream);
+}
+
+// (ayh1 null: the first backward step)
+int xde_sde_rheun_adjoint_step(void* ay0, void* ayh0, void* af0, void* ag0, const void* ay1, const void* ayh1, const void* v, int64_t n,
+                               double dt, double s, uint64_t seed, int64_t k, int dtype, void* stream) {
+  const char* who = "xde_sde_rheun_adjoint_step";
+  if (!ayh1) return rheun_launch<RheunAdjointStep<true>>(who, XDE_KID_COMBINE, {ay0, ayh0, af0, ag0}, {ay1, v}, n, dt, s, 1, seed, k, dtype, stream);
+  return rheun_launch<RheunAdjointStep<false>>(who, XDE_KID_COMBINE, {ay0, ayh0, af0, ag0}, {ay1, v, ayh1}, n, dt, s, 1, seed, k, dtype, stream);
 }
 
 }  // extern "C"

@@ -5,10 +5,14 @@ Same signature as the reference.  ``dy = drift(t, y) dt + diffusion(t, y) dW`` w
 or by the derivative-free Milstein scheme with ``solver=Milstein`` (strong order 1: a support launch, a second evaluation of
 ``diffusion`` and one xde_sde_milstein_step launch per step; element i of ``diffusion`` must depend on ``y_i`` only) or by the
 derivative-free stochastic Runge-Kutta scheme SRI1W1 with ``solver=SRK`` (strong order 1.5 under the same contract: three launches, 2
-``drift`` and 4 ``diffusion`` evaluations per step, on two in-kernel draws), the Brownian
+``drift`` and 4 ``diffusion`` evaluations per step, on two in-kernel draws) — these three read the equation in the ITO sense — or by
+the reversible Heun scheme with ``solver=ReversibleHeun``, which reads it in the STRATONOVICH sense (strong order 1 under the same
+contract, 1/2 in general: two launches, one ``drift`` and one ``diffusion`` evaluation per step; the scheme ``sdeint_adjoint``
+differentiates in memory that does not grow with the number of steps), the Brownian
 increment ``sqrt(|dt|) * Z`` generated inside the kernel (include/xde_hip_sde.h).  The reference's version never ran (its ``fuse`` is a
 TODO and it calls an ``xde.format`` that does not exist); this is the step it meant.  The result has odeint's fixed-solver layout
-``[..., T*L, D]``.  Gradients with respect to y0 and the parameters of ``drift`` and ``diffusion`` flow through the steps.
+``[..., T*L, D]``.  Gradients with respect to y0 and the parameters of ``drift`` and ``diffusion`` flow through the steps (the autograd
+graph keeps every step's operands; ``sdeint_adjoint(..., solver=ReversibleHeun)`` gives the same gradients without keeping them).
 """
 from typing import Union
 
@@ -40,7 +44,7 @@ def sdeint(
     if isinstance(y0, (tuple, list)):
         raise NotImplementedError("sdeint takes a tensor y0, not a tuple: stack the members into one state tensor")
     if not (isinstance(solver, type) and issubclass(solver, FixedSolver)):
-        raise NotImplementedError("sdeint steps with a fixed-step solver (solver=Euler, Euler-Maruyama, or solver=Milstein or SRK): adaptive steps would need "
+        raise NotImplementedError("sdeint steps with a fixed-step solver (solver=Euler, Euler-Maruyama, or solver=Milstein or SRK, or ReversibleHeun): adaptive steps would need "
                                   "a Brownian path that can be queried on any interval, which this library does not build")
     if not torch.is_tensor(t):
         t = torch.as_tensor(t)

@@ -8,7 +8,7 @@ from .base_fixed_solver import FixedSolver
 
 AdaptiveHeun, Bosh3, Dopri5, Dopri8, Fehlberg2 = _ad.AdaptiveHeun, _ad.Bosh3, _ad.Dopri5, _ad.Dopri8, _ad.Fehlberg2
 RK4, Euler, Midpoint, AdamsBashforthMoulton = _fx.RK4, _fx.Euler, _fx.Midpoint, _fx.AdamsBashforthMoulton
-Milstein, SRK = _fx.Milstein, _fx.SRK  # (sdeint only; not in __all__: the package's top level star-imports that list and keeps the reference's names)
+Milstein, SRK, ReversibleHeun = _fx.Milstein, _fx.SRK, _fx.ReversibleHeun  # (sdeint only; not in __all__: the package's top level star-imports that list and keeps the reference's names)
 
 __all__ = ["AdaptiveSolver", "AdaptiveRKSolver", "FixedSolver", "AdaptiveHeun", "Bosh3", "Dopri5", "Dopri8", "Fehlberg2", "RK4", "Euler",
            "Midpoint", "AdamsBashforthMoulton"]

@@ -1,4 +1,4 @@
-"""Autograd nodes around the step kernels (xde_stage_combine, xde_interp_rows, xde_sde_em_step, xde_sde_milstein_step, xde_sde_srk_*) for discretise-then-optimise training.
+"""Autograd nodes around the step kernels (xde_stage_combine, xde_interp_rows, xde_sde_em_step, xde_sde_milstein_step, xde_sde_srk_*, xde_sde_rheun_*) for discretise-then-optimise training.
 
 The reference trains by back-propagating through its eager solver ops (example/ode_demo.py:51-53:
 ``pred_y = odeint(func, batch_y0, t_span, solver=RK4); loss.backward()``).  Here the forward is one combine launch
@@ -233,3 +233,43 @@ class SdeSrkStepFn(torch.autograd.Function):
         g = _cotangent(g)
         rest = _sde_group_backward(ctx.backend._sde_srk_step_backward, [g], ctx.needs_input_grad[8:14], ((0, 2), (2, 6)), ctx.meta)
         return (None,) * 7 + (g if ctx.needs_input_grad[7] else None,) + rest
+
+
+class SdeRheunPredictFn(torch.autograd.Function):
+    """Reversible Heun's prediction ``yh1 = (((y0 + y0) - yh0) + f0*dt) + g0*w`` (``HipBackend._sde_rheun_predict``, direction +1) as an
+    autograd node.  The node keeps only ``(dt, s, seed, k)``: backward is xde_sde_em_backward at ``(dt, s)``, which regenerates Z and
+    writes ``gf0 = gyh1*dt`` and ``gg0 = gyh1*w``; ``gy0 = gyh1 + gyh1`` and ``gyh0 = -gyh1``."""
+
+    @staticmethod
+    def forward(ctx, backend, dt, s, seed, k, y0, yh0, f0, g0):
+        out = torch.empty_like(y0)
+        backend._sde_rheun_predict(out, y0.detach(), yh0.detach(), f0.detach(), g0.detach(), dt, s, 1, seed, k)
+        ctx.backend, ctx.meta = backend, (float(dt), float(s), int(seed), int(k))
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        needs = ctx.needs_input_grad[5:9]
+        g, gf, gg = _sde_backward(ctx.backend._sde_em_backward, g, (True,) + tuple(needs[2:]), ctx.meta)
+        return (None,) * 5 + (g + g if needs[0] else None, -g if needs[1] else None, gf, gg)
+
+
+class SdeRheunCorrectFn(torch.autograd.Function):
+    """Reversible Heun's correction ``y1 = (y0 + (f0 + f1)*(0.5*dt)) + (g0 + g1)*(0.5*w)`` (``HipBackend._sde_rheun_correct``, direction
+    +1) as an autograd node.  The node keeps only ``(dt, s, seed, k)``: backward is xde_sde_em_backward at ``(0.5*dt, 0.5*s)`` (halving
+    is exact), whose ``gf`` is the cotangent of both ``f0`` and ``f1`` and whose ``gg`` that of both ``g0`` and ``g1``; ``gy0 = gy1``."""
+
+    @staticmethod
+    def forward(ctx, backend, dt, s, seed, k, y0, f0, f1, g0, g1):
+        out = torch.empty_like(y0)
+        backend._sde_rheun_correct(out, y0.detach(), f0.detach(), f1.detach(), g0.detach(), g1.detach(), dt, s, 1, seed, k)
+        ctx.backend, ctx.meta = backend, (0.5 * float(dt), 0.5 * float(s), int(seed), int(k))
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        needs = ctx.needs_input_grad[5:10]
+        g, gf, gg = _sde_backward(ctx.backend._sde_em_backward, g, (needs[0], needs[1] or needs[2], needs[3] or needs[4]), ctx.meta)
+        return (None,) * 5 + (g, gf if needs[1] else None, gf if needs[2] else None, gg if needs[3] else None, gg if needs[4] else None)

@@ -21,7 +21,8 @@ from ..xde.base_dde import DDE_DAMPING, BaseDDE
 from ..xde.base_ode import BaseODE
 from ..xde.base_sde import BaseSDE
 from ..xde.base_xde import BaseXDE
-from ._autograd import CombineFn, InterpRowsFn, SdeEulerFn, SdeMilsteinFn, SdeSrkStage1Fn, SdeSrkStage2Fn, SdeSrkStepFn, SdeSupportFn
+from ._autograd import (CombineFn, InterpRowsFn, SdeEulerFn, SdeMilsteinFn, SdeRheunCorrectFn, SdeRheunPredictFn, SdeSrkStage1Fn, SdeSrkStage2Fn,
+                        SdeSrkStepFn, SdeSupportFn)
 from ._common import as_operand, np_dtype, storage_ptr, t_span_to_host, upload
 
 _one_third = 1 / 3
@@ -29,6 +30,12 @@ _two_thirds = 2 / 3
 _one_sixth = 1 / 6
 # what rk4_alt_step_func hands to move (FixedSolver.time_values): dt, dt/3, t0 + dt/3, t0 + 2dt/3 (base_fixed_solver.py:168-174)
 RK4_ALT_TIME_VALUES = ((1.0, False), (_one_third, False), (_one_third, True), (_two_thirds, True))
+
+
+def sde_step_scalars(dt, dtype):
+    """``(dt, s)`` of an SDE step as the kernels take them (Python floats): ``s = sqrt(|dt|)`` computed in float64 from the host ``dt``
+    (time dtype) and rounded to the state dtype."""
+    return float(dt), float(np_dtype(dtype)(np.sqrt(abs(np.float64(dt)))))
 
 
 def _step_size_value(step_size):
@@ -114,7 +121,7 @@ class _SubSteps:
 class FixedSolver(metaclass=abc.ABCMeta):
     order: int
 
-    steps_sde = False  # the step is a convergent scheme for Ito SDEs (a BaseSDE problem): Euler, as Euler-Maruyama, Milstein and SRK
+    steps_sde = False  # the step is a convergent scheme for SDEs (a BaseSDE problem): Euler, as Euler-Maruyama, Milstein and SRK (Ito), ReversibleHeun (Stratonovich)
 
     graphable = True  # the step's control flow does not depend on data (False: AdamsBashforthMoulton)
     GRAPH_MIN_STEPS = 4
@@ -171,7 +178,7 @@ class FixedSolver(metaclass=abc.ABCMeta):
         if self._sde:
             if not self.steps_sde:
                 raise NotImplementedError("{} does not step SDEs: its tableau does not converge for Ito SDEs; use Euler "
-                                          "(Euler-Maruyama) or Milstein or SRK".format(type(self).__name__))
+                                          "(Euler-Maruyama) or Milstein or SRK (or ReversibleHeun, Stratonovich)".format(type(self).__name__))
             if pipeline == "graph":
                 raise NotImplementedError("pipeline='graph' replays one captured step, which cannot advance the SDE's grid-step "
                                           "counter; use pipeline='sync' (or the default 'auto', which keeps the eager loop for SDEs)")
@@ -189,6 +196,7 @@ class FixedSolver(metaclass=abc.ABCMeta):
         self.backend = _hip.get_backend()
         self.nfe = 0
         self._tdev_cache = {}
+        self._carry = None  # ReversibleHeun: the (yh, fh, gh) the last step left
 
     # -- per-step state ---------------------------------------------------------------------------
     def _arm(self, dt=None, t0_host=None, row=None, y1_out=None, k=None, ctrls=None, rec=None):
@@ -312,6 +320,36 @@ class FixedSolver(metaclass=abc.ABCMeta):
         self.backend._sde_srk_step(out, y0, a1, a2, b1, b2, b3, b4, dt, s, c, c3, seed, k)
         return out, a1
 
+    def _rheun_step(self, t0, t1, dtt, y0, dt):
+        """One reversible Heun step of a BaseSDE (Kidger, Foster, Li, Lyons 2021: Stratonovich, diagonal noise), two launches around the
+        one evaluation they feed (the formulas in their written op order: include/xde_hip_sde.h) — predict writes
+        ``yh1 = (((y0 + y0) - yh0) + fh0*dt) + gh0*w``; then ``fh1 = drift(t1, yh1)``, ``gh1 = diffusion(t1, yh1)``; correct writes
+        ``y1 = (y0 + (fh0 + fh1)*(0.5*dt)) + (gh0 + gh1)*(0.5*w)``, ``w = s*Z`` on the Z of (xde.seed, grid step k) as in ``_em_step``.
+        The carried ``(yh, fh, gh)`` lives in ``self._carry``: at grid step 0 and on a step() outside a walk it is
+        ``(y0, drift(t0, y0), diffusion(t0, y0))``, afterwards what the step before left.  Through SdeRheunPredictFn /
+        SdeRheunCorrectFn when an operand is differentiated.  ``nfe`` counts steps.  Returns ``(y1, fh0)``."""
+        self.nfe += 1
+        xde, seed = self.xde, self.xde.seed
+        k = self._k if self._k is not None else 0
+        if not self._k or self._carry is None:
+            f, g = self.move(t0, dtt, y0)
+            self._carry = (y0, as_operand(f, like=y0), as_operand(g, like=y0))
+        yh0, f0, g0 = self._carry
+        dt, s = sde_step_scalars(dt, y0.dtype)
+        grad = torch.is_grad_enabled() and any(x.requires_grad for x in (y0, yh0, f0, g0))
+        if grad:
+            yh1 = SdeRheunPredictFn.apply(self.backend, dt, s, seed, k, y0, yh0, f0, g0)
+        else:
+            yh1 = torch.empty_like(y0)
+            self.backend._sde_rheun_predict(yh1, y0, yh0, f0, g0, dt, s, 1, seed, k)
+        f1, g1 = as_operand(xde.call_func(t1, yh1), like=y0), as_operand(xde.diffusion(t1, yh1), like=y0)
+        self._carry = (yh1, f1, g1)
+        if grad or (torch.is_grad_enabled() and (f1.requires_grad or g1.requires_grad)):
+            return SdeRheunCorrectFn.apply(self.backend, dt, s, seed, k, y0, f0, f1, g0, g1), f0
+        out = self._y1_out if self._y1_out is not None else torch.empty_like(y0)
+        self.backend._sde_rheun_correct(out, y0, f0, f1, g0, g1, dt, s, 1, seed, k)
+        return out, f0
+
     def _combine_pre(self, y0, pre, ks, coef, dt, scale, out=None):
         """The final weighted sum with its leading terms pre-summed (xde_stage_combine_pre_weighted): reads y0, ``pre`` and the newest
         derivative(s)."""
@@ -375,6 +413,10 @@ class FixedSolver(metaclass=abc.ABCMeta):
 
     # -- base_fixed_solver.py:103-144 ------------------------------------------------------------
     def integrate(self, t_span):
+        return self._walk(*self._plan(t_span))
+
+    def _plan(self, t_span):
+        """What ``_walk`` takes for a solve over the output times ``t_span``: ``(grid, grid_dev, plan, pred_len)``."""
         if not torch.is_tensor(t_span):
             t_span = torch.as_tensor(t_span)
         y0 = self.y0
@@ -387,9 +429,9 @@ class FixedSolver(metaclass=abc.ABCMeta):
         if grid is t_host or np.array_equal(grid, t_host):  # (a grid that IS t_span: the plain plan, bit for bit)
             # (values rounded to the time dtype on the host, as t_span.astype would; no blocking pageable copy)
             t_dev = t_span.detach().to(device=y0.device, dtype=t_dtype) if t_span.is_cuda else upload(t_host, y0.device)
-            return self._walk(t_host, t_dev, _SubSteps(t_host, None, self.interp), len(t_host))
+            return t_host, t_dev, _SubSteps(t_host, None, self.interp), len(t_host)
         plan = _SubSteps(t_host, grid, self.interp)  # (validated before the first launch)
-        return self._walk(grid, upload(grid, y0.device), plan, len(t_host))
+        return grid, upload(grid, y0.device), plan, len(t_host)
 
     def _grid(self, t_host, t_span):
         """The grid of a sub-stepped solve (step_size / grid_constructor) on the host, in the time dtype, validated (before anything

@@ -1,4 +1,5 @@
-"""Euler (reference: paddlexde/solver/fixed_solver/euler.py:4-11)."""
+"""Euler (reference: paddlexde/solver/fixed_solver/euler.py:4-11).  Under sdeint it is Euler-Maruyama and reads the equation in the Ito sense,
+as Milstein and SRK do; ReversibleHeun is the one Stratonovich solver."""
 from ... import _hip
 from ..base_fixed_solver import FixedSolver
 

@@ -1,4 +1,5 @@
-"""Milstein: strong order 1.0 steps for Ito SDEs with diagonal noise (the derivative-free form; FixedSolver._milstein_step)."""
+"""Milstein: strong order 1.0 steps for Ito SDEs with diagonal noise (the derivative-free form; FixedSolver._milstein_step).  Ito, as Euler and SRK under
+sdeint; ReversibleHeun is the one Stratonovich solver."""
 from ..base_fixed_solver import FixedSolver
 
 

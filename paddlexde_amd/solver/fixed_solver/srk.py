@@ -1,4 +1,5 @@
-"""SRK: strong order 1.5 steps for Ito SDEs with diagonal noise (Roessler's derivative-free SRI1W1; FixedSolver._srk_step)."""
+"""SRK: strong order 1.5 steps for Ito SDEs with diagonal noise (Roessler's derivative-free SRI1W1; FixedSolver._srk_step).  Ito, as
+Euler and Milstein under sdeint; ReversibleHeun is the one Stratonovich solver."""
 from ..base_fixed_solver import FixedSolver
 
 
