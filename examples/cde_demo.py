@@ -1,0 +1,100 @@
+#!/usr/bin/env python3
+"""Neural-CDE demo on paddlexde_amd: tell clockwise spirals from anticlockwise ones.
+
+Data (generated from a seed, nothing downloaded): ``n`` spirals of ``length`` points ``(time, x, y)`` with a random phase and a little
+noise, half of them turning each way.  Model: the control ``X`` is the cubic Hermite spline through each series (time is a channel, the
+knots are the unit grid); ``z0 = initial(X.evaluate(t0))``, ``dz = f_theta(z) dX`` with an MLP field returning ``[B, H, C]``, and a
+linear read-out of ``z`` at the last time gives the logit (loss: binary cross-entropy).  Trained through ``cdeint`` with RK4 on the
+knots (gradients through the steps), or with ``--adjoint`` through ``cdeint_adjoint`` with Dopri5 (the continuous adjoint).
+
+    python examples/cde_demo.py --max-steps 60 [--adjoint]
+"""
+import argparse
+import math
+import os
+import sys
+import time
+
+import torch
+import torch.nn as nn
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from paddlexde_amd.functional import cdeint, cdeint_adjoint  # noqa: E402
+from paddlexde_amd.interpolation import CubicHermiteSpline  # noqa: E402
+from paddlexde_amd.solver import RK4, Dopri5  # noqa: E402
+
+CHANNELS = 3  # (time, x, y)
+
+
+def make_data(n=128, length=32, seed=0, device="cuda:0"):
+    """series [n, length, 3] and labels [n] (1: clockwise)."""
+    gen = torch.Generator().manual_seed(seed)
+    t = torch.linspace(0.0, 4.0 * math.pi, length)
+    phase = 2.0 * math.pi * torch.rand(n, 1, generator=gen)
+    labels = (torch.arange(n) % 2).float()
+    sign = (1.0 - 2.0 * labels)[:, None]  # anticlockwise: +1, clockwise: -1
+    r = 1.0 / (1.0 + 0.2 * t)[None, :]
+    x = r * torch.cos(phase + sign * t[None, :]) + 0.01 * torch.randn(n, length, generator=gen)
+    y = r * torch.sin(phase + sign * t[None, :]) + 0.01 * torch.randn(n, length, generator=gen)
+    series = torch.stack([t[None, :].expand(n, -1), x, y], dim=-1)
+    return series.to(device), labels.to(device)
+
+
+class CDEFunc(nn.Module):
+    """f_theta: z [B, H] -> [B, H, C]."""
+
+    def __init__(self, hidden):
+        super().__init__()
+        self.net = nn.Sequential(nn.Linear(hidden, 32), nn.Tanh(), nn.Linear(32, hidden * CHANNELS), nn.Tanh())
+
+    def forward(self, t, z):
+        return self.net(z).reshape(z.shape + (CHANNELS,))
+
+
+class NeuralCDE(nn.Module):
+    def __init__(self, hidden=8):
+        super().__init__()
+        self.initial = nn.Linear(CHANNELS, hidden)
+        self.func = CDEFunc(hidden)
+        self.readout = nn.Linear(hidden, 1)
+
+    def forward(self, X, adjoint=False):
+        knots = X.grid_points
+        z0 = self.initial(X.evaluate(knots[:1])[:, 0, :])  # [B, H]
+        if adjoint:
+            zT = cdeint_adjoint(self.func, X, z0, knots[[0, -1]], solver=Dopri5, rtol=1e-3, atol=1e-5)[-1]
+        else:
+            zT = cdeint(self.func, X, z0, knots, RK4).reshape(knots.numel(), *z0.shape)[-1]  # (fixed solvers stack time on axis -2)
+        return self.readout(zT)[:, 0]
+
+
+def train(max_steps=60, n=128, length=32, hidden=8, seed=0, device="cuda:0", adjoint=False, log_every=10):
+    torch.manual_seed(seed)
+    series, labels = make_data(n, length, seed, device)
+    X = CubicHermiteSpline(series)
+    model = NeuralCDE(hidden).to(device)
+    opt = torch.optim.Adam(model.parameters(), lr=1e-2)
+    losses = []
+    t0 = time.perf_counter()
+    for step in range(1, max_steps + 1):
+        logits = model(X, adjoint)
+        loss = nn.functional.binary_cross_entropy_with_logits(logits, labels)
+        opt.zero_grad()
+        loss.backward()
+        opt.step()
+        losses.append(loss.item())
+        if log_every and step % log_every == 0:
+            acc = ((logits > 0).float() == labels).float().mean().item()
+            print("Iter {:04d} | Loss {:.6f} | Accuracy {:.3f} | {:.1f} it/s".format(step, losses[-1], acc, step / (time.perf_counter() - t0)),
+                  flush=True)
+    return losses
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--max-steps", type=int, default=60)
+    ap.add_argument("--adjoint", action="store_true", help="train through cdeint_adjoint (Dopri5) instead of cdeint (RK4)")
+    a = ap.parse_args()
+    ls = train(a.max_steps, adjoint=a.adjoint)
+    print("first loss {:.4f} -> last loss {:.4f}".format(ls[0], ls[-1]))

@@ -203,10 +203,16 @@ SDE_PROTOTYPES = {
     "xde_sde_rheun_adjoint_stage": (_i32, [_vp] * 5 + [_i64, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
     "xde_sde_rheun_adjoint_step": (_i32, [_vp] * 7 + [_i64, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
 }
+# the entry points of include/xde_hip_cde.h (cdeint's control-derivative contraction and its cotangent); bound by load_library() after _bind_sde
+CDE_PROTOTYPES = {
+    "xde_cde_contract": (_i32, [_vp] * 5 + [_dbl, _i32, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "xde_cde_contract_backward": (_i32, [_vp] * 5 + [_dbl, _i32, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),
+}
 SYMBOLS = tuple(PROTOTYPES)
 BACKPROP_SYMBOLS = tuple(BACKPROP_PROTOTYPES)
 GRID_SYMBOLS = tuple(GRID_PROTOTYPES)
 SDE_SYMBOLS = tuple(SDE_PROTOTYPES)
+CDE_SYMBOLS = tuple(CDE_PROTOTYPES)
 XDE_INTERP_MAX_ROWS = 8
 XDE_INTERP_LINEAR, XDE_INTERP_CUBIC = 0, 1
 XDE_ROW_INTERP, XDE_ROW_COPY_A, XDE_ROW_COPY_B = 0, 1, 2
@@ -238,7 +244,7 @@ _REBUILD = "rebuild it with `python -m paddlexde_amd.csrc.build --force`"
 
 
 def _declare(lib, sym):
-    proto = PROTOTYPES.get(sym) or BACKPROP_PROTOTYPES.get(sym) or GRID_PROTOTYPES.get(sym) or SDE_PROTOTYPES[sym]
+    proto = PROTOTYPES.get(sym) or BACKPROP_PROTOTYPES.get(sym) or GRID_PROTOTYPES.get(sym) or SDE_PROTOTYPES.get(sym) or CDE_PROTOTYPES[sym]
     try:
         fn = getattr(lib, sym)
     except AttributeError:
@@ -278,6 +284,12 @@ def _bind_sde(lib):
         _declare(lib, sym)
 
 
+def _bind_cde(lib):
+    """Declare the entry points of include/xde_hip_cde.h on ``lib`` (after ``_bind``: the ABI check comes first)."""
+    for sym in CDE_SYMBOLS:
+        _declare(lib, sym)
+
+
 def load_library():
     """dlopen libxde_hip.so and declare prototypes.  Raises if it has not been built, or is not the library this binding speaks to."""
     global _lib
@@ -295,6 +307,7 @@ def load_library():
         _bind(lib)
         _bind_grid(lib)
         _bind_sde(lib)
+        _bind_cde(lib)
         _lib = lib
     return _lib
 
@@ -902,6 +915,46 @@ class HipBackend:
             return
         rc = self.lib.xde_sde_noise(out.data_ptr(), out.numel(), int(seed), int(k), mode, dt, self._stream(out))
         self._check(rc, "xde_sde_noise")
+
+    # -- cdeint's vector field (include/xde_hip_cde.h) ----------------------------------------------------------------------------------
+    # Private for the reason _interp_rows is: the public methods are the contract tests/_cpu_double.py mirrors.  Only CdeContractFn
+    # (xde/base_cde.py) calls these.
+    def _cde_call(self, who, out, src, series, knots, t, method):
+        """One launch of ``xde<who>``: ``series [B, Tn, C]``, ``knots [Tn]``, the big operand ``[B, H, C]`` and the small one ``[B, H]``
+        contiguous on the device in one dtype; ``t`` a one-element float32 / float64 device tensor (read by the kernel: no host
+        synchronisation, and a captured launch replays with its current value) or a Python number."""
+        big, small = (src, out) if who == "_cde_contract" else (out, src)
+        self._require_device(out, src, series, knots)
+        if series.dim() != 3 or big.dim() != 3 or small.dim() != 2:
+            raise XdeError("{}: expected series [B, Tn, C], F [B, H, C] and out [B, H]".format(who))
+        B, Tn, C = series.shape
+        H = big.shape[1]
+        if tuple(big.shape) != (B, H, C) or tuple(small.shape) != (B, H) or tuple(knots.shape) != (Tn,):
+            raise XdeError("{}: shapes do not agree: series {}, knots {}, F {}, out {}".format(
+                who, tuple(series.shape), tuple(knots.shape), tuple(big.shape), tuple(small.shape)))
+        for x in (out, src, series, knots):
+            if not x.is_contiguous() or x.dtype != series.dtype or x.device != series.device:
+                raise XdeError("{}: the operands must be contiguous tensors of one dtype on one device".format(who))
+        if torch.is_tensor(t):
+            self._require_device(t)
+            if t.numel() != 1 or t.dtype not in (torch.float32, torch.float64) or t.device != series.device:
+                raise XdeError("{}: t must be ONE float32 / float64 element on the series' device (got shape {}, {}, {})".format(
+                    who, tuple(t.shape), t.dtype, t.device))
+            t_dev, t_host, tt = t.data_ptr(), 0.0, dtype_code(t.dtype)
+        else:
+            t_dev, t_host, tt = None, float(t), XDE_F64
+        rc = getattr(self.lib, "xde" + who)(out.data_ptr(), src.data_ptr(), series.data_ptr(), knots.data_ptr(), t_dev, t_host, tt, B, H, C,
+                                            Tn, HISTORY_METHODS[method], dtype_code(series.dtype), self._stream(series))
+        self._check(rc, "xde" + who)
+
+    def _cde_contract(self, out, F, series, knots, t, method):
+        """``out[b, h] = sum_c F[b, h, c] * dX[b, c]`` with ``dX`` the derivative at ``t`` of the ``method`` ("linear" | "cubic") spline
+        through ``series`` over ``knots``, in the summation order of include/xde_hip_cde.h.  One launch; dX is never written."""
+        self._cde_call("_cde_contract", out, F, series, knots, t, method)
+
+    def _cde_contract_backward(self, gF, gout, series, knots, t, method):
+        """``gF[b, h, c] = gout[b, h] * dX[b, c]``: the cotangent of ``_cde_contract``'s F.  One launch."""
+        self._cde_call("_cde_contract_backward", gF, gout, series, knots, t, method)
 
     def hermite_gather(self, val, der, his, his_t, lags):
         """his [..., T, D] (contiguous), his_t [T], lags [L]  ->  val, der [..., L, D]."""

@@ -13,6 +13,7 @@
 // K4: lazy dense output; cubic-Hermite history gather of the DDE caller.
 
 #include "xde_common.hpp"
+#include "xde_spline_device.hpp"
 
 using namespace xde;
 
@@ -189,35 +190,11 @@ __global__ __launch_bounds__(kBlock) void xde_hermite_kernel(T* __restrict__ val
     const int d = int(e % D);
     const int l = int((e / D) % L);
     const int64_t o = e / (int64_t(D) * L);
-    const T tau = lags[l];
-    // index = clip(bucketize(tau, t) - 1, 0, T-1); bucketize (right=False) = #{ t_i < tau }
-    int lo = 0, hi = Tn;
-    while (lo < hi) {
-      int mid = (lo + hi) >> 1;
-      if (ts[mid] < tau) lo = mid + 1; else hi = mid;
-    }
-    int i = lo - 1;
-    i = i < 0 ? 0 : (i > Tn - 1 ? Tn - 1 : i);
-    auto h_at = [&](int j) -> T {  // scale1[j] = t[j+1]-t[j], last one repeated
-      int jj = j < Tn - 1 ? j : Tn - 2;
-      return ts[jj + 1] - ts[jj];
-    };
-    const T h1 = h_at(i);                 // scale1[i]
-    const T h2 = i == 0 ? h_at(0) : h_at(i - 1);  // scale2[i] = concat(scale[:1], scale1[:-1])[i]
-    const T s = (tau - ts[i]) / h1;
+    // index = clip(bucketize(tau, t) - 1, 0, T-1), the Hermite basis and the one-sided node differences: xde_spline_device.hpp
+    const HermiteLag<T> r = make_hermite_lag<T>(ts, lags[l], Tn);
     const T* row = his + o * int64_t(Tn) * D + d;
-    auto ser = [&](int j) -> T { return row[int64_t(j < Tn ? j : Tn - 1) * D]; };
-    auto drv = [&](int j) -> T {  // derivs has T+1 entries: finite differences, the last two repeat the last one
-      int jj = j < Tn - 1 ? j : Tn - 2;
-      return (ser(jj + 1) - ser(jj)) / h_at(jj);
-    };
-    const T p0 = ser(i) / h1, p1 = ser(i + 1) / h2, d0 = drv(i), d1 = drv(i + 1);
-    // [s^3, s^2, s, 1] @ H  and  [3s^2, 2s, 1, 0] @ H  with H = [[2,-2,1,1],[-3,3,-2,-1],[0,0,1,0],[1,0,0,0]]
-    const T s2 = s * s, s3 = s2 * s;
-    const T c0 = T(2) * s3 - T(3) * s2 + T(1), c1 = T(-2) * s3 + T(3) * s2, c2 = s3 - T(2) * s2 + s, c3 = s3 - s2;
-    const T g0 = T(6) * s2 - T(6) * s, g1 = T(-6) * s2 + T(6) * s, g2 = T(3) * s2 - T(4) * s + T(1), g3 = T(3) * s2 - T(2) * s;
-    val[e] = (((c0 * p0 + c1 * p1) + c2 * d0) + c3 * d1) * h1;  // evaluate(): result *= scale
-    der[e] = ((g0 * p0 + g1 * p1) + g2 * d0) + g3 * d1;         // derivative(): no scale factor
+    const int i1 = r.i + 1 < Tn ? r.i + 1 : Tn - 1;
+    hermite_eval<T>(r, row[int64_t(r.i) * D], row[int64_t(i1) * D], row[int64_t(r.zrow) * D], val[e], der[e]);
   }
 }
 
@@ -225,12 +202,7 @@ __global__ __launch_bounds__(kBlock) void xde_hermite_kernel(T* __restrict__ val
 // builds the per-lag table (interval index, Hermite basis values, the interval widths, which rows feed the two node
 // derivatives) in LDS once, then streams 16-byte vectors along D: three row loads, two stores per output vector.
 constexpr int kHermiteMaxL = 128;
-template <typename T>
-struct HermiteLag {
-  int i, mode, zrow, pad;  // mode 0: interior; 1: i == T-2 (d1 repeats d0's rows); 2: i == T-1 (both use rows T-2, T-1)
-  T h1, h2, ha, hb, c0, c1, c2, c3, g0, g1, g2, g3;
-};
-
+// (HermiteLag / make_hermite_lag / hermite_eval: xde_spline_device.hpp, shared with the CDE contraction)
 template <typename T>
 __global__ __launch_bounds__(kBlock) void xde_hermite_vec_kernel(T* __restrict__ val, T* __restrict__ der,
                                                                  const T* __restrict__ his, const T* __restrict__ ts,
@@ -239,38 +211,7 @@ __global__ __launch_bounds__(kBlock) void xde_hermite_vec_kernel(T* __restrict__
   constexpr int W = P::W;
   __shared__ HermiteLag<T> tab[kHermiteMaxL];
   for (int l = threadIdx.x; l < L; l += kBlock) {
-    const T tau = lags[l];
-    int lo = 0, hi = Tn;
-    while (lo < hi) {
-      int mid = (lo + hi) >> 1;
-      if (ts[mid] < tau) lo = mid + 1; else hi = mid;
-    }
-    int i = lo - 1;
-    i = i < 0 ? 0 : (i > Tn - 1 ? Tn - 1 : i);
-    auto h_at = [&](int j) -> T {
-      int jj = j < Tn - 1 ? j : Tn - 2;
-      return ts[jj + 1] - ts[jj];
-    };
-    HermiteLag<T> r;
-    r.i = i;
-    r.mode = i <= Tn - 3 ? 0 : (i == Tn - 2 ? 1 : 2);
-    r.zrow = r.mode == 0 ? i + 2 : Tn - 2;
-    r.pad = 0;
-    r.h1 = h_at(i);
-    r.h2 = i == 0 ? h_at(0) : h_at(i - 1);
-    r.ha = h_at(i);
-    r.hb = h_at(i + 1);
-    const T sx = (tau - ts[i]) / r.h1;
-    const T s2 = sx * sx, s3 = s2 * sx;
-    r.c0 = T(2) * s3 - T(3) * s2 + T(1);
-    r.c1 = T(-2) * s3 + T(3) * s2;
-    r.c2 = s3 - T(2) * s2 + sx;
-    r.c3 = s3 - s2;
-    r.g0 = T(6) * s2 - T(6) * sx;
-    r.g1 = T(-6) * s2 + T(6) * sx;
-    r.g2 = T(3) * s2 - T(4) * sx + T(1);
-    r.g3 = T(3) * s2 - T(2) * sx;
-    tab[l] = r;
+    tab[l] = make_hermite_lag<T>(ts, lags[l], Tn);
   }
   __syncthreads();
   const int DV = D / W;
@@ -300,12 +241,7 @@ __global__ __launch_bounds__(kBlock) void xde_hermite_vec_kernel(T* __restrict__
     P v, g;
 #pragma unroll
     for (int x = 0; x < W; ++x) {
-      const T p0 = X.v[x] / r.h1, p1 = Y.v[x] / r.h2;
-      const T n0 = r.mode == 2 ? X.v[x] - Z.v[x] : Y.v[x] - X.v[x];
-      const T n1 = r.mode == 0 ? Z.v[x] - Y.v[x] : n0;
-      const T d0 = n0 / r.ha, d1 = n1 / r.hb;
-      v.v[x] = (((r.c0 * p0 + r.c1 * p1) + r.c2 * d0) + r.c3 * d1) * r.h1;
-      g.v[x] = ((r.g0 * p0 + r.g1 * p1) + r.g2 * d0) + r.g3 * d1;
+      hermite_eval<T>(r, X.v[x], Y.v[x], Z.v[x], v.v[x], g.v[x]);
     }
     v.store(val, e);
     g.store(der, e);

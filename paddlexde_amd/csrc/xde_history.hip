@@ -16,6 +16,7 @@
 // once per workgroup in LDS.
 
 #include "xde_common.hpp"
+#include "xde_spline_device.hpp"
 
 using namespace xde;
 
@@ -23,77 +24,7 @@ namespace {
 
 constexpr int kHistMaxL = 128;  // lags per LAUNCH (the LDS table); more lags are served in tiles of this many
 
-template <typename T>
-struct RowsLag {
-  int row[4];      // his rows min(i + k, T - 1)
-  T wv[4], wd[4];  // weight of row k (of `his[row] / scale{k+1}`: the reference divides the SERIES, then weights it) in value / derivative
-  T h1;            // scale1_i
-};
-
-// the per-lag table entry (one thread per lag)
-template <typename T, int M>
-__device__ __forceinline__ RowsLag<T> make_lag(const T* __restrict__ ts, T tau, int Tn) {
-  constexpr int SPAN = M == 2 ? 1 : 3;  // scale = t[j + SPAN] - t[j], j < T - SPAN
-  int lo = 0, hi = Tn;
-  while (lo < hi) {
-    int mid = (lo + hi) >> 1;
-    if (ts[mid] < tau) lo = mid + 1; else hi = mid;
-  }
-  int i = lo - 1;  // bucketize(tau, t) - 1 with right=False: #{t_j < tau} - 1
-  i = i < 0 ? 0 : (i > Tn - 1 ? Tn - 1 : i);
-  auto scale1 = [&](int j) -> T {  // concat(scale, scale[-1:] * SPAN)[j]
-    int jj = j < Tn - SPAN ? j : Tn - SPAN - 1;
-    return ts[jj + SPAN] - ts[jj];
-  };
-  RowsLag<T> r;
-  r.h1 = scale1(i);
-  const T s = (tau - ts[i]) / r.h1;
-  T w[4] = {T(0), T(0), T(0), T(0)}, g[4] = {T(0), T(0), T(0), T(0)};
-  if (M == 2) {
-    // [s, 1] @ [[-1, 1], [1, 0]] = [-s + 1, s];  [1, 0] @ H = [-1, 1]
-    w[0] = -s + T(1);
-    w[1] = s;
-    g[0] = T(-1);
-    g[1] = T(1);
-  } else {
-    // [s^3, s^2, s, 1] @ H,  [3 s^2, 2 s, 1, 0] @ H  with H = [[-1,3,-3,1],[3,-6,3,0],[-3,3,0,0],[1,0,0,0]]
-    const T s2 = s * s, s3 = s2 * s;
-    w[0] = ((-s3 + T(3) * s2) - T(3) * s) + T(1);
-    w[1] = (T(3) * s3 - T(6) * s2) + T(3) * s;
-    w[2] = T(-3) * s3 + T(3) * s2;
-    w[3] = s3;
-    const T a = T(3) * s2, b = T(2) * s;
-    g[0] = (-a + T(3) * b) - T(3);
-    g[1] = (T(3) * a - T(6) * b) + T(3);
-    g[2] = T(-3) * a + T(3) * b;
-    g[3] = a;
-  }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    r.row[k] = i + k < Tn ? i + k : Tn - 1;
-    r.wv[k] = w[k];
-    r.wd[k] = g[k];
-  }
-  return r;
-}
-
-template <typename T>
-struct RowsScale {
-  T sc[4];
-};
-
-template <typename T, int M>
-__device__ __forceinline__ RowsScale<T> make_scales(const T* __restrict__ ts, int i, int Tn) {
-  constexpr int SPAN = M == 2 ? 1 : 3;
-  auto scale1 = [&](int j) -> T {
-    int jj = j < Tn - SPAN ? j : Tn - SPAN - 1;
-    return ts[jj + SPAN] - ts[jj];
-  };
-  RowsScale<T> q;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) q.sc[k] = scale1(i - k < 0 ? 0 : i - k);
-  return q;
-}
+// (RowsLag / make_lag / RowsScale / make_scales / rows_eval: xde_spline_device.hpp, shared with the CDE contraction)
 
 template <typename T, int M, bool VEC>
 __global__ __launch_bounds__(kBlock) void xde_rows_gather_kernel(T* __restrict__ val, T* __restrict__ der, const T* __restrict__ his,
@@ -129,16 +60,10 @@ __global__ __launch_bounds__(kBlock) void xde_rows_gather_kernel(T* __restrict__
     P v, g;
 #pragma unroll
     for (int x = 0; x < W; ++x) {
-      T av = r.wv[0] * (X[0].v[x] / q.sc[0]);
-      T ad = r.wd[0] * (X[0].v[x] / q.sc[0]);
+      T xs[M];
 #pragma unroll
-      for (int k = 1; k < M; ++k) {
-        const T p = X[k].v[x] / q.sc[k];
-        av = av + r.wv[k] * p;
-        ad = ad + r.wd[k] * p;
-      }
-      v.v[x] = av * r.h1;  // evaluate(): result *= scale
-      g.v[x] = ad;         // derivative(): no scale factor
+      for (int k = 0; k < M; ++k) xs[k] = X[k].v[x];
+      rows_eval<T, M>(r, q, xs, v.v[x], g.v[x]);
     }
     v.store_nt(val, at);
     g.store_nt(der, at);

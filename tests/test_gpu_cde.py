@@ -1,0 +1,201 @@
+"""cdeint on the GPU: xde_cde_contract / xde_cde_contract_backward against the numpy double bit for bit (every branch of the kernels:
+below one vector, unaligned, one vector, more than one team pass, the grid exceeded, the scalar path, every kind of time), two checks
+that do not go through the double (the identity field returns X.derivative(t); the standard summation bound against a float64 dot), a
+refused call leaving its output standing, the end-to-end cases of tests/_cde_cases.py on the HIP backend, the captured adjoint dynamics
+against the eager one, and the demo."""
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from paddlexde_amd import _hip
+from paddlexde_amd.interpolation import CubicHermiteSpline, LinearInterpolation
+
+from . import _cde_oracle as CO
+from ._cde_cases import *  # noqa: F401,F403
+from ._cde_cases import Field, _field, _grads, cdeint_adjoint, inputs, Dopri5
+from ._cde_double import CdeDoubleBackend
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+_NPT = {torch.float32: np.float32, torch.float64: np.float64}
+SENTINEL = 7.0
+SPLINE = {"linear": LinearInterpolation, "cubic": CubicHermiteSpline}
+
+
+@pytest.fixture
+def dev():
+    return DEV
+
+
+def _placed(x, misalign):
+    """``x`` (numpy) on the device, contiguous, 16-byte aligned or one element off it."""
+    flat = torch.empty(x.size + 1, dtype=torch.from_numpy(x).dtype, device=DEV)
+    view = (flat[1:] if misalign else flat[:-1]).view(x.shape)
+    view.copy_(torch.from_numpy(x))
+    assert (view.data_ptr() % 16 != 0) == bool(misalign)
+    return view
+
+
+def _times(knots, Tn):
+    """first knot, exactly on an interior knot (the first one where there is none), inside the last interval, the last knot"""
+    return [float(knots[0]), float(knots[1 if Tn > 2 else 0]), float(knots[-1] - 0.25 * (knots[-1] - knots[-2])), float(knots[-1])]
+
+
+def _time_forms(t, dtype):
+    """the time as a float64 device scalar (also with a float32 series), as a [1] device tensor of the series dtype, as a host number"""
+    return [torch.tensor(t, dtype=torch.float64, device=DEV), torch.tensor([t], dtype=dtype, device=DEV), t]
+
+
+def _check(double, dtype, method, B, H, C, Tn, t, form, misalign=False, seed=0):
+    be = _hip.get_backend()
+    T = _NPT[dtype]
+    rs = np.random.RandomState(seed + 1000 * C + 10 * H + B)
+    series, F, gout = rs.randn(B, Tn, C).astype(T), rs.randn(B, H, C).astype(T), rs.randn(B, H).astype(T)
+    knots = np.cumsum(0.5 + rs.rand(Tn)).astype(T)  # (an irregular grid: the scale conventions as written)
+    tv = _times(knots, Tn)[t]
+    th = torch.from_numpy
+    want, gwant = torch.empty(B, H, dtype=dtype), torch.empty(B, H, C, dtype=dtype)
+    cpu_t = [torch.tensor(tv, dtype=torch.float64), torch.tensor([tv], dtype=dtype), tv][form]
+    double._cde_contract(want, th(F), th(series), th(knots), cpu_t, method)
+    double._cde_contract_backward(gwant, th(gout), th(series), th(knots), cpu_t, method)
+    ser_d, kn_d = _placed(series, False), _placed(knots, False)
+    out = _placed(np.full((B, H), SENTINEL, dtype=T), misalign)
+    gF = _placed(np.full((B, H, C), SENTINEL, dtype=T), misalign)
+    td = _time_forms(tv, dtype)[form]
+    be._cde_contract(out, _placed(F, misalign), ser_d, kn_d, td, method)
+    be._cde_contract_backward(gF, _placed(gout, misalign), ser_d, kn_d, td, method)
+    where = (dtype, method, B, H, C, Tn, tv, form, misalign)
+    assert np.array_equal(out.cpu().numpy(), want.numpy()), where
+    assert np.array_equal(gF.cpu().numpy(), gwant.numpy()), where
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
+@pytest.mark.parametrize("method", ["linear", "cubic"])
+def test_the_kernels_equal_the_double_bit_for_bit(dtype, method):
+    """C below one vector, unaligned, one vector, many, more than one team pass (260 > 64 W in both dtypes); H and B around a
+    workgroup's teams; Tn 2, 3, 8; every kind and form of time; the scalar path (operands one element off 16 bytes) gives the aligned
+    bits — both equal the double's."""
+    double = CdeDoubleBackend()
+    n = 0
+    for C in (1, 3, 4, 5, 64, 260):
+        for H in (1, 7, 33):
+            for B in (1, 3):
+                Tn = (2, 3, 8)[n % 3]
+                for t in range(4):
+                    _check(double, dtype, method, B, H, C, Tn, t, form=(n + t) % 3)
+                _check(double, dtype, method, B, H, C, Tn, t=2, form=0, misalign=True)
+                n += 1
+    assert double.launches.count("cde_contract") == double.launches.count("cde_contract_backward") == 36 * 5
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
+def test_more_work_items_than_the_grid(dtype):
+    """B * H exceeds the grid once: B = 2100, H = 1, C = 3.  Short rows of consecutive batch rows share a work item where B is
+    large, so two more shapes: B = 2101 (the last item holds one batch row, not two), and B = 4200, H = 512, C = 1, where the
+    grouped items (2100 of two batch rows each) still exceed the grid and a workgroup takes a second one."""
+    double = CdeDoubleBackend()
+    for method in ("linear", "cubic"):
+        _check(double, dtype, method, 2100, 1, 3, 8, t=2, form=0)
+        _check(double, dtype, method, 2101, 1, 3, 3, t=1, form=1)
+        _check(double, dtype, method, 4200, 512, 1, 2, t=2, form=2)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
+def test_a_row_longer_than_the_on_chip_table(dtype):
+    """C = 2050 > the 2048 channels of dX a workgroup keeps in LDS: the derivative is recomputed per use, same bits."""
+    double = CdeDoubleBackend()
+    for method in ("linear", "cubic"):
+        _check(double, dtype, method, 2, 3, 2050, 3, t=2, form=1)
+        _check(double, dtype, method, 2, 3, 2050, 3, t=1, form=2, misalign=True)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
+@pytest.mark.parametrize("method", ["linear", "cubic"])
+def test_the_identity_field_returns_the_spline_derivative(dtype, method):
+    """H = C and F[b] = I: the output is X.derivative(t), the `der` of xde_history_gather, bit for bit (not through the double)."""
+    be = _hip.get_backend()
+    rs = np.random.RandomState(5)
+    for C, Tn in ((1, 2), (3, 3), (5, 8), (64, 8), (260, 8)):
+        series = torch.from_numpy(rs.randn(3, Tn, C).astype(_NPT[dtype])).to(DEV)
+        knots = torch.from_numpy(np.cumsum(0.5 + rs.rand(Tn)).astype(_NPT[dtype])).to(DEV)
+        X = SPLINE[method](series, knots)
+        F = torch.eye(C, dtype=dtype, device=DEV).expand(3, C, C).contiguous()
+        for tv in _times(knots.cpu().numpy(), Tn):
+            t = torch.tensor([tv], dtype=dtype, device=DEV)
+            out = torch.full((3, C), SENTINEL, dtype=dtype, device=DEV)
+            be._cde_contract(out, F, X._series, X._t, t, method)
+            assert torch.equal(out, X.derivative(t)[:, 0, :]), (C, Tn, tv)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
+def test_the_sum_is_within_the_standard_bound_of_the_float64_dot(dtype):
+    """Against the float64 dot of the same rounded operands (F and the X.derivative(t) the device wrote): |err| <= gamma_C sum|F dX|,
+    gamma_C = C u / (1 - C u), valid for any summation order (not through the double)."""
+    be = _hip.get_backend()
+    rs = np.random.RandomState(6)
+    for C in (1, 5, 64, 260):
+        series = torch.from_numpy(rs.randn(3, 8, C).astype(_NPT[dtype])).to(DEV)
+        X = CubicHermiteSpline(series)
+        F = torch.from_numpy(rs.randn(3, 33, C).astype(_NPT[dtype])).to(DEV)
+        t = torch.tensor(3.6, dtype=torch.float64, device=DEV)
+        out = torch.empty(3, 33, dtype=dtype, device=DEV)
+        be._cde_contract(out, F, X._series, X._t, t, "cubic")
+        dX = X.derivative(t)[:, 0, :].double().cpu().numpy()
+        Fd = F.double().cpu().numpy()
+        err = np.abs(out.double().cpu().numpy() - np.einsum("bhc,bc->bh", Fd, dX))
+        bound = CO.gamma(C, _NPT[dtype]) * np.einsum("bhc,bc->bh", np.abs(Fd), np.abs(dX))
+        print("C = {}, {}: worst err / bound = {:.3g}".format(C, dtype, float((err / bound).max())))
+        assert (err <= bound).all()
+
+
+def test_a_refused_call_leaves_the_output_standing():
+    be = _hip.get_backend()
+    series, knots = torch.randn(2, 5, 4, device=DEV), torch.arange(5.0, device=DEV)
+    F, g = torch.randn(2, 3, 4, device=DEV), torch.randn(2, 3, device=DEV)
+    out, gF = torch.full((2, 3), SENTINEL, device=DEV), torch.full((2, 3, 4), SENTINEL, device=DEV)
+    st = be._stream(out)
+    for sym, dst, src in (("xde_cde_contract", out, F), ("xde_cde_contract_backward", gF, g)):
+        fn = getattr(be.lib, sym)
+        good = [dst.data_ptr(), src.data_ptr(), series.data_ptr(), knots.data_ptr(), None, 1.5, 1, 2, 3, 4, 5, 0, 0, st]
+        for i, v in ((1, None), (2, None), (3, None), (7, 0), (8, 0), (9, 0), (10, 1), (11, 2), (11, 9), (12, 2), (6, 2)):
+            args = list(good)
+            args[i] = v
+            assert fn(*args) == _hip.XDE_EBADARG, (sym, i, v)
+        with pytest.raises(_hip.XdeError, match="XDE_HISTORY_BEZIER is not a control path"):
+            (be._cde_contract if dst is out else be._cde_contract_backward)(dst, src, series, knots, 1.5, "bez")
+        torch.cuda.synchronize()
+        assert bool((dst == SENTINEL).all())
+        assert fn(*good) == _hip.XDE_OK
+        torch.cuda.synchronize()
+        assert not bool((dst == SENTINEL).any())
+
+
+def test_the_captured_adjoint_dynamics_give_the_eager_gradients_bit_for_bit(dev):
+    """cdeint_adjoint with adjoint_options["graph_func"] = True (the contraction and its cotangent inside a captured HIP graph, the
+    time read from device memory at every replay) against graph_func = False."""
+    series, _, z0 = inputs(torch.float64)
+    X = CubicHermiteSpline(torch.from_numpy(series).to(dev))
+    z0 = torch.from_numpy(z0).to(dev)
+    ts = torch.linspace(0.0, 7.0, 4, dtype=torch.float64).to(dev)
+    field = _field(dev)
+
+    def grads(captured):
+        loss = lambda z: cdeint_adjoint(field, X, z, ts, solver=Dopri5, adjoint_options={"graph_func": captured}).square().sum()  # noqa: E731
+        return _grads(loss, field, z0)
+
+    eager, captured = grads(False), grads(True)
+    for a, b in zip(eager, captured):
+        assert np.abs(a).max() > 0 and np.array_equal(a, b)
+
+
+@pytest.mark.parametrize("adjoint", [False, True])
+def test_cde_demo_loss_falls(adjoint):
+    """examples/cde_demo.py for a few iterations, through the steps and through the adjoint."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "examples"))
+    import cde_demo
+
+    losses = cde_demo.train(max_steps=8, n=32, length=16, adjoint=adjoint, log_every=0)
+    assert all(np.isfinite(losses)) and sum(losses[-3:]) < 0.9 * sum(losses[:3]), losses
