@@ -49,6 +49,29 @@ int xde_cde_contract(void* out, const void* F, const void* series, const void* k
 int xde_cde_contract_backward(void* gF, const void* gout, const void* series, const void* knots, const void* t_dev, double t_host,
                               int time_dtype, int64_t B, int H, int C, int Tn, int method, int dtype, void* stream);
 
+/* THE LAUNCH PLAN.  What the host decides about a launch of either entry point from (B, H, C, dtype) and the 16-byte alignment of the
+ * big operand: which kernel instantiation runs and how its rows are dealt to workgroups.  The bits of the result never depend on it;
+ * it is reported so that a test can state which code a shape runs, whatever the tuning constants are. */
+typedef struct xde_cde_plan {
+  int32_t vec;           /* 16-byte vector loads / stores of the big operand (C % W == 0 and it is 16-byte aligned), else scalar */
+  int32_t lds;           /* dX rows are kept in LDS (else recomputed per use: C is beyond the on-chip table) */
+  int32_t grouped;       /* Gb > 1: consecutive batch rows share a work item */
+  int32_t R;             /* forward: lanes per (b, h) row team; backward: 1 */
+  int32_t single;        /* forward: a lane holds at most one vector of a row (else it strides along the row); backward: 0 */
+  int32_t S, Hc;         /* slices of H per batch row, rows per slice (the last slice may be shorter) */
+  int32_t Gb;            /* batch rows per work item (the last item may hold fewer) */
+  int32_t rows_per_pass; /* rows of the big operand one workgroup covers before it walks on along its work item */
+  int32_t nt;            /* forward: F is read with the streaming policy; backward: 0 */
+  int64_t items;         /* work items: B * S, or ceil(B / Gb) */
+  int64_t blocks;        /* workgroups launched: min(items, the grid cap); a workgroup takes items blocks apart */
+} xde_cde_plan_t;
+
+/* The plan of xde_cde_contract (backward == 0: `big` is F) or xde_cde_contract_backward (backward != 0: `big` is gF) into *plan, by
+ * the function the launch itself uses.  Enqueues nothing and needs no device; `big` is used for its alignment only and never
+ * dereferenced.  Refused (XDE_EBADARG): a null plan, B < 1, H < 1, C < 1, a dtype that is not XDE_F32 / XDE_F64, a `big` not aligned
+ * to its element type. */
+int xde_cde_plan(int backward, const void* big, int64_t B, int H, int C, int dtype, xde_cde_plan_t* plan);
+
 #ifdef __cplusplus
 }
 #endif

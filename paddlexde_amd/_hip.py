@@ -203,10 +203,18 @@ SDE_PROTOTYPES = {
     "xde_sde_rheun_adjoint_stage": (_i32, [_vp] * 5 + [_i64, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
     "xde_sde_rheun_adjoint_step": (_i32, [_vp] * 7 + [_i64, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
 }
+class XdeCdePlan(C.Structure):
+    """Mirror of xde_cde_plan_t (include/xde_hip_cde.h)."""
+
+    _fields_ = [(name, C.c_int32) for name in ("vec", "lds", "grouped", "R", "single", "S", "Hc", "Gb", "rows_per_pass", "nt")] + [
+        ("items", C.c_int64), ("blocks", C.c_int64)]
+
+
 # the entry points of include/xde_hip_cde.h (cdeint's control-derivative contraction and its cotangent); bound by load_library() after _bind_sde
 CDE_PROTOTYPES = {
     "xde_cde_contract": (_i32, [_vp] * 5 + [_dbl, _i32, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),
     "xde_cde_contract_backward": (_i32, [_vp] * 5 + [_dbl, _i32, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "xde_cde_plan": (_i32, [_i32, _vp, _i64, _i32, _i32, _i32, C.POINTER(XdeCdePlan)]),
 }
 SYMBOLS = tuple(PROTOTYPES)
 BACKPROP_SYMBOLS = tuple(BACKPROP_PROTOTYPES)
@@ -955,6 +963,14 @@ class HipBackend:
     def _cde_contract_backward(self, gF, gout, series, knots, t, method):
         """``gF[b, h, c] = gout[b, h] * dX[b, c]``: the cotangent of ``_cde_contract``'s F.  One launch."""
         self._cde_call("_cde_contract_backward", gF, gout, series, knots, t, method)
+
+    def _cde_plan(self, backward, big, B, H, channels):
+        """The launch plan of ``_cde_contract`` (``backward`` false: ``big`` is F) or ``_cde_contract_backward`` (``big`` is gF) for
+        ``[B, H, channels]``, ``big``'s dtype and its alignment, as a dict of xde_cde_plan_t's fields.  Nothing is enqueued."""
+        plan = XdeCdePlan()
+        rc = self.lib.xde_cde_plan(int(bool(backward)), big.data_ptr(), int(B), int(H), int(channels), dtype_code(big.dtype), C.byref(plan))
+        self._check(rc, "xde_cde_plan")
+        return {name: int(getattr(plan, name)) for name, _ in XdeCdePlan._fields_}
 
     def hermite_gather(self, val, der, his, his_t, lags):
         """his [..., T, D] (contiguous), his_t [T], lags [L]  ->  val, der [..., L, D]."""

@@ -291,23 +291,61 @@ int cde_check(const std::string& who, const void* out, const void* in, const voi
 }
 
 // slices of H per batch row: one (a workgroup reads series[b] once) unless B alone leaves most of the chip idle
-void cde_slices(CdeArgs* a, int64_t rows_per_pass, int64_t full_pass) {
+void cde_slices(xde_cde_plan_t* p, int64_t B, int H, int C, int64_t rows_per_pass, int64_t full_pass) {
   constexpr int64_t kWant = 1024;  // work items that fill the chip
-  int64_t S = (kWant + a->B - 1) / a->B;
-  const int64_t most = (int64_t(a->H) + rows_per_pass - 1) / rows_per_pass;  // a slice is at least one pass of the workgroup
+  int64_t S = (kWant + B - 1) / B;
+  const int64_t most = (int64_t(H) + rows_per_pass - 1) / rows_per_pass;  // a slice is at least one pass of the workgroup
   if (S > most) S = most;
   if (S < 1) S = 1;
-  a->Hc = int((int64_t(a->H) + S - 1) / S);
-  a->S = (a->H + a->Hc - 1) / a->Hc;
+  p->Hc = int((int64_t(H) + S - 1) / S);
+  p->S = (H + p->Hc - 1) / p->Hc;
   // batch rows per item: where a batch row's H rows leave most of the workgroup's pass idle, consecutive batch rows share an item (more
   // independent loads in flight per workgroup, fewer barriers) — as long as their dX rows fit the LDS table and the chip stays full
-  a->Gb = 1;
-  if (a->S == 1 && a->lds) {
-    int64_t G = full_pass / a->H;
-    if (G > kCdeMaxC / a->C) G = kCdeMaxC / a->C;
-    if (G > a->B / kWant) G = a->B / kWant;
-    if (G > 1) a->Gb = int(G);
+  p->Gb = 1;
+  if (p->S == 1 && p->lds) {
+    int64_t G = full_pass / H;
+    if (G > kCdeMaxC / C) G = kCdeMaxC / C;
+    if (G > B / kWant) G = B / kWant;
+    if (G > 1) p->Gb = int(G);
   }
+}
+
+// everything the host decides about a launch, from the direction, the sizes, the dtype and the big operand's alignment: the ONE
+// statement of it — the launchers run what it returns, xde_cde_plan reports it
+xde_cde_plan_t cde_plan(bool backward, const void* big, int64_t B, int H, int C, int dtype) {
+  const int width = dtype == XDE_F32 ? 4 : 2;
+  xde_cde_plan_t p;
+  memset(&p, 0, sizeof(p));
+  p.vec = (C % width) == 0 && aligned16(big);
+  p.lds = C <= kCdeMaxC;
+  if (!backward) {
+    const int NV = (C + width - 1) / width;
+    p.R = NV < 64 ? pow2ceil(NV) : 64;
+    p.single = NV <= p.R;
+    const int TPB = kBlock / p.R;  // row teams of a workgroup
+    p.rows_per_pass = p.single ? kCdeRows * TPB : TPB;
+    cde_slices(&p, B, H, C, TPB, p.single ? int64_t(kCdeRows) * TPB : 0);
+    p.nt = big_operand(B * int64_t(H) * C, dtype) ? 1 : 0;
+  } else {
+    p.R = 1;
+    const int per = p.vec ? C / width : C;
+    p.rows_per_pass = per < kBlock ? kBlock / per : 1;
+    cde_slices(&p, B, H, C, p.rows_per_pass, per < kBlock ? int64_t(kCdeRows) * p.rows_per_pass : 0);
+  }
+  p.grouped = p.Gb > 1;
+  p.items = p.S > 1 ? B * p.S : (B + p.Gb - 1) / p.Gb;
+  p.blocks = p.items > grid_cap() ? grid_cap() : p.items;
+  return p;
+}
+
+void cde_args(CdeArgs* a, const xde_cde_plan_t& p, void* out, const void* in, const void* series, const void* knots, const void* t_dev,
+              double t_host, int time_dtype, int64_t B, int H, int C, int Tn, int method) {
+  memset(a, 0, sizeof(*a));
+  a->out = out, a->in = in, a->series = series, a->knots = knots, a->t_dev = t_dev, a->t_host = t_host;
+  a->B = B, a->H = H, a->C = C, a->Tn = Tn, a->method = method, a->time_f64 = time_dtype == XDE_F64;
+  a->R = p.R;
+  for (a->r_log = 0; (1 << a->r_log) < a->R; ++a->r_log) {}
+  a->S = p.S, a->Hc = p.Hc, a->Gb = p.Gb, a->lds = p.lds, a->nt = p.nt;
 }
 
 }  // namespace
@@ -315,13 +353,13 @@ void cde_slices(CdeArgs* a, int64_t rows_per_pass, int64_t full_pass) {
 // (a launch that groups batch rows keeps their dX rows in LDS: GRP implies LDSDX)
 #define CDE_DISPATCH(KERNEL, TY)                                                                          \
   do {                                                                                                    \
-    if (vec) {                                                                                            \
-      if (a.Gb > 1) XDE_LAUNCH((KERNEL<TY, true, true, true>), g, blk, st, prof, a);                      \
-      else if (lds) XDE_LAUNCH((KERNEL<TY, true, true, false>), g, blk, st, prof, a);                     \
+    if (p.vec) {                                                                                          \
+      if (p.grouped) XDE_LAUNCH((KERNEL<TY, true, true, true>), g, blk, st, prof, a);                     \
+      else if (p.lds) XDE_LAUNCH((KERNEL<TY, true, true, false>), g, blk, st, prof, a);                   \
       else XDE_LAUNCH((KERNEL<TY, true, false, false>), g, blk, st, prof, a);                             \
     } else {                                                                                              \
-      if (a.Gb > 1) XDE_LAUNCH((KERNEL<TY, false, true, true>), g, blk, st, prof, a);                     \
-      else if (lds) XDE_LAUNCH((KERNEL<TY, false, true, false>), g, blk, st, prof, a);                    \
+      if (p.grouped) XDE_LAUNCH((KERNEL<TY, false, true, true>), g, blk, st, prof, a);                    \
+      else if (p.lds) XDE_LAUNCH((KERNEL<TY, false, true, false>), g, blk, st, prof, a);                  \
       else XDE_LAUNCH((KERNEL<TY, false, false, false>), g, blk, st, prof, a);                            \
     }                                                                                                     \
   } while (0)
@@ -331,25 +369,13 @@ extern "C" {
 int xde_cde_contract(void* out, const void* F, const void* series, const void* knots, const void* t_dev, double t_host, int time_dtype,
                      int64_t B, int H, int C, int Tn, int method, int dtype, void* stream) {
   if (int rc = cde_check("xde_cde_contract", out, F, series, knots, t_dev, time_dtype, B, H, C, Tn, method, dtype)) return rc;
-  const int width = dtype == XDE_F32 ? 4 : 2;
+  const xde_cde_plan_t p = cde_plan(false, F, B, H, C, dtype);
   CdeArgs a;
-  memset(&a, 0, sizeof(a));
-  a.out = out, a.in = F, a.series = series, a.knots = knots, a.t_dev = t_dev, a.t_host = t_host;
-  a.B = B, a.H = H, a.C = C, a.Tn = Tn, a.method = method, a.time_f64 = time_dtype == XDE_F64;
-  const int NV = (C + width - 1) / width;
-  a.R = NV < 64 ? pow2ceil(NV) : 64;
-  for (a.r_log = 0; (1 << a.r_log) < a.R; ++a.r_log) {}
-  const bool lds = C <= kCdeMaxC;
-  a.lds = lds;
-  cde_slices(&a, kBlock / a.R, NV <= a.R ? int64_t(kCdeRows) * (kBlock / a.R) : 0);
-  a.nt = big_operand(B * int64_t(H) * C, dtype) ? 1 : 0;
-  const bool vec = (C % width) == 0 && aligned16(F);
-  int64_t blocks = a.S > 1 ? B * a.S : (B + a.Gb - 1) / a.Gb;
-  if (blocks > grid_cap()) blocks = grid_cap();
+  cde_args(&a, p, out, F, series, knots, t_dev, t_host, time_dtype, B, H, C, Tn, method);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const double es = dtype == XDE_F32 ? 4.0 : 8.0;
   ProfScope prof(XDE_KID_DENSE, (double(B) * H * C + double(B) * H + 3.0 * double(B) * C) * es);
-  dim3 g(static_cast<unsigned>(blocks)), blk(kBlock);
+  dim3 g(static_cast<unsigned>(p.blocks)), blk(kBlock);
   if (dtype == XDE_F32) CDE_DISPATCH(xde_cde_contract_kernel, float);
   else CDE_DISPATCH(xde_cde_contract_kernel, double);
   HIP_TRY(hipGetLastError());
@@ -359,26 +385,26 @@ int xde_cde_contract(void* out, const void* F, const void* series, const void* k
 int xde_cde_contract_backward(void* gF, const void* gout, const void* series, const void* knots, const void* t_dev, double t_host,
                               int time_dtype, int64_t B, int H, int C, int Tn, int method, int dtype, void* stream) {
   if (int rc = cde_check("xde_cde_contract_backward", gF, gout, series, knots, t_dev, time_dtype, B, H, C, Tn, method, dtype)) return rc;
-  const int width = dtype == XDE_F32 ? 4 : 2;
+  const xde_cde_plan_t p = cde_plan(true, gF, B, H, C, dtype);
   CdeArgs a;
-  memset(&a, 0, sizeof(a));
-  a.out = gF, a.in = gout, a.series = series, a.knots = knots, a.t_dev = t_dev, a.t_host = t_host;
-  a.B = B, a.H = H, a.C = C, a.Tn = Tn, a.method = method, a.time_f64 = time_dtype == XDE_F64;
-  a.R = 1;
-  const bool vec = (C % width) == 0 && aligned16(gF);
-  const bool lds = C <= kCdeMaxC;
-  const int per = vec ? C / width : C;
-  a.lds = lds;
-  cde_slices(&a, per < kBlock ? kBlock / per : 1, per < kBlock ? int64_t(kCdeRows) * (kBlock / per) : 0);
-  int64_t blocks = a.S > 1 ? B * a.S : (B + a.Gb - 1) / a.Gb;
-  if (blocks > grid_cap()) blocks = grid_cap();
+  cde_args(&a, p, gF, gout, series, knots, t_dev, t_host, time_dtype, B, H, C, Tn, method);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const double es = dtype == XDE_F32 ? 4.0 : 8.0;
   ProfScope prof(XDE_KID_DENSE, (double(B) * H * C + double(B) * H + 3.0 * double(B) * C) * es);
-  dim3 g(static_cast<unsigned>(blocks)), blk(kBlock);
+  dim3 g(static_cast<unsigned>(p.blocks)), blk(kBlock);
   if (dtype == XDE_F32) CDE_DISPATCH(xde_cde_backward_kernel, float);
   else CDE_DISPATCH(xde_cde_backward_kernel, double);
   HIP_TRY(hipGetLastError());
+  return XDE_OK;
+}
+
+int xde_cde_plan(int backward, const void* big, int64_t B, int H, int C, int dtype, xde_cde_plan_t* plan) {
+  if (!plan) return fail(XDE_EBADARG, "xde_cde_plan: null pointer");
+  if (B < 1 || H < 1 || C < 1) return fail(XDE_EBADARG, "xde_cde_plan: bad sizes (need B, H, C >= 1)");
+  if (dtype != XDE_F32 && dtype != XDE_F64) return fail(XDE_EBADARG, "xde_cde_plan: bad dtype");
+  if (reinterpret_cast<uintptr_t>(big) & (dtype == XDE_F32 ? 3u : 7u))
+    return fail(XDE_EBADARG, "xde_cde_plan: operand not aligned to its element type");
+  *plan = cde_plan(backward != 0, big, B, H, C, dtype);
   return XDE_OK;
 }
 

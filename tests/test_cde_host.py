@@ -1,6 +1,7 @@
 """cdeint without a GPU: the end-to-end cases of tests/_cde_cases.py on the numpy double, the launches of a walk and of its backward,
 the double against tests/_cde_oracle.py, every refusal by message, and the C ABI of include/xde_hip_cde.h (every call below is refused
 on the host before anything is enqueued)."""
+import ctypes
 import os
 import re
 import subprocess
@@ -15,9 +16,11 @@ from paddlexde_amd import _hip
 from . import _cde_oracle as CO
 from ._cde_cases import *  # noqa: F401,F403
 from ._cde_cases import B, C, H, T, Field, _field, cdeint, cdeint_adjoint, inputs, CubicHermiteSpline, LinearInterpolation, RK4, Dopri5
+from . import _cde_plans as P
 from ._cde_double import CdeDoubleBackend, contract_in_header_order, team_lanes
 from .test_srk_host import _entry
 
+LAUNCHES = ("xde_cde_contract", "xde_cde_contract_backward")  # (the entry points that enqueue: one signature)
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "xde_hip_cde.h")
 
@@ -182,7 +185,8 @@ def test_cde_entry_points_validate_their_arguments_on_the_host():
               ({}, dict(dtype=2)), ({}, dict(dtype=-1)), ({}, dict(time_dtype=2)), ({}, dict(time_dtype=-1)),
               ({}, dict(method=2)), ({}, dict(method=3)), ({}, dict(method=-1)),
               ({0: A + 2}, {}), ({1: 2 * A + 4}, dict(dtype=1)), ({4: 5 * A + 2}, dict(time_dtype=0)), ({4: 5 * A + 4}, {})])
-    for name in _hip.CDE_SYMBOLS:
+    assert set(_hip.CDE_SYMBOLS) == set(LAUNCHES) | {"xde_cde_plan"}  # (the plan query has its own test below)
+    for name in LAUNCHES:
         fn = _entry(lib, name, 5, scalars)
         for ptrs, kw in bad:
             for extra in ({}, {4: None}) if 4 not in ptrs else ({},):  # (with the time in device memory, and as a host number)
@@ -207,3 +211,92 @@ def test_the_cde_backend_methods_are_private():
     assert not any("cde" in m for m in pub)
     for m in ("_cde_contract", "_cde_contract_backward"):
         assert callable(getattr(_hip.HipBackend, m)) and callable(getattr(CdeDoubleBackend, m))
+    assert callable(_hip.HipBackend._cde_plan)
+
+
+# ----------------------------------------------------------------------------------------------
+# the launch plan (host arithmetic: no device)
+# ----------------------------------------------------------------------------------------------
+def host_plan(backward, dt, B, H, C, misalign):
+    """xde_cde_plan for a big operand that is 16-byte aligned or one element off it (the pointer is never dereferenced)."""
+    plan = _hip.XdeCdePlan()
+    at = 0x10000 + (0 if not misalign else 4 if dt == "f32" else 8)
+    rc = _hip.load_library().xde_cde_plan(int(backward), at, B, H, C, _hip.XDE_F32 if dt == "f32" else _hip.XDE_F64, ctypes.byref(plan))
+    assert rc == _hip.XDE_OK, _hip.load_library().xde_last_error()
+    return {name: int(getattr(plan, name)) for name, _ in _hip.XdeCdePlan._fields_}
+
+
+def test_the_plan_struct_mirrors_the_header():
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    body = re.search(r"typedef struct xde_cde_plan \{(.*?)\} xde_cde_plan_t;", src, flags=re.S).group(1)
+    want = []
+    for ctype, names in re.findall(r"(int32_t|int64_t)\s+([^;]+);", body):
+        want += [(n.strip(), ctypes.c_int32 if ctype == "int32_t" else ctypes.c_int64) for n in names.split(",")]
+    assert want == list(_hip.XdeCdePlan._fields_) and len(want) == 12
+    assert ctypes.sizeof(_hip.XdeCdePlan) == 10 * 4 + 2 * 8
+
+
+def test_the_plan_query_validates_its_arguments():
+    lib = _hip.load_library()
+    plan = _hip.XdeCdePlan()
+    good = dict(backward=0, big=0x10000, B=2, H=3, C=4, dtype=0)
+    sizes, align = "bad sizes (need B, H, C >= 1)", "operand not aligned to its element type"
+    for kw, msg in ((dict(B=0), sizes), (dict(H=0), sizes), (dict(C=-1), sizes), (dict(dtype=2), "bad dtype"),
+                    (dict(big=0x10002), align), (dict(big=0x10004, dtype=1), align)):
+        a = dict(good, **kw)
+        assert lib.xde_cde_plan(a["backward"], a["big"], a["B"], a["H"], a["C"], a["dtype"], ctypes.byref(plan)) == _hip.XDE_EBADARG, kw
+        assert lib.xde_last_error().decode() == "xde_cde_plan: " + msg
+    assert lib.xde_cde_plan(0, 0x10000, 2, 3, 4, 0, None) == _hip.XDE_EBADARG and lib.xde_last_error().decode() == "xde_cde_plan: null pointer"
+    assert lib.xde_cde_plan(0, None, 2, 3, 4, 0, ctypes.byref(plan)) == _hip.XDE_OK  # (only the alignment of `big` is used)
+
+
+def test_the_plan_of_the_plainest_launch():
+    """B, H, C = 2, 4, 3 (tests/_cde_cases.py): what the fields mean, on the one shape whose plan follows from the header alone —
+    C = 3 is one fp32 vector (R = 1) and two fp64 ones (R = 2), no whole vector, so scalar loads; C fits the on-chip table; two
+    batch rows are two items on two workgroups, far from the grid cap, and F is far from the streaming threshold."""
+    for dt, R in (("f32", 1), ("f64", 2)):
+        for backward in (False, True):
+            p = host_plan(backward, dt, B, H, C, False)
+            assert (p["vec"], p["lds"], p["grouped"], p["Gb"], p["nt"]) == (0, 1, 0, 1, 0)
+            assert p["items"] == p["blocks"] == B * p["S"] and p["S"] * p["Hc"] >= H > (p["S"] - 1) * p["Hc"] and p["rows_per_pass"] >= 1
+            assert (p["R"], p["single"]) == ((1, 0) if backward else (R, 1))
+    # alignment decides vec where C is whole vectors, and only there
+    assert host_plan(False, "f32", 2, 4, 8, False)["vec"] == 1 and host_plan(False, "f32", 2, 4, 8, True)["vec"] == 0
+    assert host_plan(True, "f64", 2, 4, 6, False)["vec"] == 1 and host_plan(True, "f64", 2, 4, 5, False)["vec"] == 0
+
+
+@pytest.mark.parametrize("dt", ["f32", "f64"])
+def test_every_row_of_the_plan_table_takes_its_branches(dt):
+    """tests/_cde_plans.py: each row's shape takes the branches the row is there for (the GPU test launches them and asserts this again
+    on the pointers it launches with)."""
+    missed = []
+    for row in P.TABLE:
+        (B_, H_, C_), fwd, bwd = P.row_case(row, dt)
+        for backward, want in ((False, fwd), (True, bwd)):
+            got = P.features(host_plan(backward, dt, B_, H_, C_, row.misalign), B_, H_, C_, backward)
+            if not want <= got:
+                missed.append((row.label, "backward" if backward else "forward", "not taken:", sorted(want - got)))
+    assert missed == []
+
+
+@pytest.mark.parametrize("dt", ["f32", "f64"])
+def test_the_suites_shapes_reach_every_reachable_plan(dt):
+    """Over every shape tests/test_gpu_cde.py launches: all six instantiations, a second item in each family, a second row pass in
+    each path, a short last slice, a short last group and the streaming loads — forward and backward."""
+    assert P.coverage_gaps(host_plan, dt) == []
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_the_double_is_within_the_standard_bound_at_the_plan_tables_row_lengths(dtype):
+    """contract_in_header_order against the float64 einsum of the same rounded operands at C = 8, 256, 2052 (the row lengths the plan
+    table adds): |err| <= gamma_C sum|F dX|, the bound of a length-C inner product in any order — so the bits the kernels are held to
+    at those lengths do not rest on the double alone."""
+    rs = np.random.RandomState(8)
+    for Cc in (8, 256, 2052):
+        F, dX = rs.randn(3, 5, Cc).astype(dtype), rs.randn(3, Cc).astype(dtype)
+        got = contract_in_header_order(F, dX)
+        assert got.dtype == dtype and got.shape == (3, 5)
+        Fd, dXd = F.astype(np.float64), dX.astype(np.float64)
+        err = np.abs(got.astype(np.float64) - np.einsum("bhc,bc->bh", Fd, dXd))
+        bound = CO.gamma(Cc, dtype) * np.einsum("bhc,bc->bh", np.abs(Fd), np.abs(dXd))
+        assert (err <= bound).all(), (Cc, float((err / bound).max()))

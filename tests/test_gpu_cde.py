@@ -1,9 +1,12 @@
-"""cdeint on the GPU: xde_cde_contract / xde_cde_contract_backward against the numpy double bit for bit (every branch of the kernels:
-below one vector, unaligned, one vector, more than one team pass, the grid exceeded, the scalar path, every kind of time), two checks
-that do not go through the double (the identity field returns X.derivative(t); the standard summation bound against a float64 dot), a
-refused call leaving its output standing, the end-to-end cases of tests/_cde_cases.py on the HIP backend, the captured adjoint dynamics
-against the eager one, and the demo."""
+"""cdeint on the GPU: xde_cde_contract / xde_cde_contract_backward against the numpy double bit for bit (below one vector, unaligned,
+one vector, more than one team pass, the scalar path, every kind of time, inside and outside the knots; and a table of shapes,
+tests/_cde_plans.py, that reaches every launch plan the default settings can reach — each row held to its plan through xde_cde_plan,
+the union held to full coverage — with the one plan they cannot reach, a sliced launch beyond the grid, in a child process), the
+autograd wrapper at two of those shapes, two checks that do not go through the double (the identity field returns X.derivative(t); the
+standard summation bound against a float64 dot), a refused call leaving its output standing, the end-to-end cases of
+tests/_cde_cases.py on the HIP backend, the captured adjoint dynamics against the eager one, and the demo."""
 import os
+import subprocess
 import sys
 
 import numpy as np
@@ -13,7 +16,10 @@ import torch
 from paddlexde_amd import _hip
 from paddlexde_amd.interpolation import CubicHermiteSpline, LinearInterpolation
 
+from paddlexde_amd.xde.base_cde import CdeContractFn
+
 from . import _cde_oracle as CO
+from . import _cde_plans as P
 from ._cde_cases import *  # noqa: F401,F403
 from ._cde_cases import Field, _field, _grads, cdeint_adjoint, inputs, Dopri5
 from ._cde_double import CdeDoubleBackend
@@ -23,6 +29,8 @@ DEV = "cuda:0"
 _NPT = {torch.float32: np.float32, torch.float64: np.float64}
 SENTINEL = 7.0
 SPLINE = {"linear": LinearInterpolation, "cubic": CubicHermiteSpline}
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+_DT = {torch.float32: "f32", torch.float64: "f64"}
 
 
 @pytest.fixture
@@ -40,8 +48,13 @@ def _placed(x, misalign):
 
 
 def _times(knots, Tn):
-    """first knot, exactly on an interior knot (the first one where there is none), inside the last interval, the last knot"""
-    return [float(knots[0]), float(knots[1 if Tn > 2 else 0]), float(knots[-1] - 0.25 * (knots[-1] - knots[-2])), float(knots[-1])]
+    """0-3: first knot, exactly on an interior knot (the first one where there is none), inside the last interval, the last knot;
+    4-7: strictly inside the first interval, strictly inside a middle one (Tn = 8: the fourth of seven), before the first knot,
+    beyond the last knot (the header defines dX for any tau: the interval index is clipped)"""
+    m = (Tn - 1) // 2
+    return [float(knots[0]), float(knots[1 if Tn > 2 else 0]), float(knots[-1] - 0.25 * (knots[-1] - knots[-2])), float(knots[-1]),
+            float(knots[0] + 0.25 * (knots[1] - knots[0])), float(knots[m] + 0.5 * (knots[m + 1] - knots[m])),
+            float(knots[0] - 0.75 * (knots[1] - knots[0])), float(knots[-1] + 1.5 * (knots[-1] - knots[-2]))]
 
 
 def _time_forms(t, dtype):
@@ -49,7 +62,16 @@ def _time_forms(t, dtype):
     return [torch.tensor(t, dtype=torch.float64, device=DEV), torch.tensor([t], dtype=dtype, device=DEV), t]
 
 
+def _query(backward, dt, B, H, C, misalign):
+    """The launch plan for a big operand placed as ``_placed`` places it (only its alignment enters the plan)."""
+    big = torch.empty(8, dtype=torch.float32 if dt == "f32" else torch.float64, device=DEV)[1 if misalign else 0:]
+    assert (big.data_ptr() % 16 != 0) == bool(misalign)
+    return _hip.get_backend()._cde_plan(backward, big, B, H, C)
+
+
 def _check(double, dtype, method, B, H, C, Tn, t, form, misalign=False, seed=0):
+    """Both kernels against the double, bit for bit.  Returns the branches (tests/_cde_plans.py: ``features``) the two launches took,
+    from the plans of the operands they were launched with."""
     be = _hip.get_backend()
     T = _NPT[dtype]
     rs = np.random.RandomState(seed + 1000 * C + 10 * H + B)
@@ -65,11 +87,13 @@ def _check(double, dtype, method, B, H, C, Tn, t, form, misalign=False, seed=0):
     out = _placed(np.full((B, H), SENTINEL, dtype=T), misalign)
     gF = _placed(np.full((B, H, C), SENTINEL, dtype=T), misalign)
     td = _time_forms(tv, dtype)[form]
-    be._cde_contract(out, _placed(F, misalign), ser_d, kn_d, td, method)
+    F_d = _placed(F, misalign)
+    be._cde_contract(out, F_d, ser_d, kn_d, td, method)
     be._cde_contract_backward(gF, _placed(gout, misalign), ser_d, kn_d, td, method)
     where = (dtype, method, B, H, C, Tn, tv, form, misalign)
     assert np.array_equal(out.cpu().numpy(), want.numpy()), where
     assert np.array_equal(gF.cpu().numpy(), gwant.numpy()), where
+    return P.features(be._cde_plan(False, F_d, B, H, C), B, H, C, False), P.features(be._cde_plan(True, gF, B, H, C), B, H, C, True)
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
@@ -93,14 +117,98 @@ def test_the_kernels_equal_the_double_bit_for_bit(dtype, method):
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
 def test_more_work_items_than_the_grid(dtype):
-    """B * H exceeds the grid once: B = 2100, H = 1, C = 3.  Short rows of consecutive batch rows share a work item where B is
-    large, so two more shapes: B = 2101 (the last item holds one batch row, not two), and B = 4200, H = 512, C = 1, where the
-    grouped items (2100 of two batch rows each) still exceed the grid and a workgroup takes a second one."""
+    """Short rows of consecutive batch rows share a work item where B is large.  B = 2100, H = 1, C = 3 is grouped (scalar kernel: C
+    is no whole vector), every item a full group, and the items stay within the grid; B = 2101: the last item holds fewer batch rows
+    than the others; B = 4200, H = 512, C = 1: the grouped items still exceed the grid, so a workgroup takes a second one, and the
+    backward kernel walks each item in more than one pass.  (The ungrouped and no-LDS kernels beyond the grid: the plan table below.)"""
     double = CdeDoubleBackend()
     for method in ("linear", "cubic"):
-        _check(double, dtype, method, 2100, 1, 3, 8, t=2, form=0)
-        _check(double, dtype, method, 2101, 1, 3, 3, t=1, form=1)
-        _check(double, dtype, method, 4200, 512, 1, 2, t=2, form=2)
+        fwd, bwd = _check(double, dtype, method, 2100, 1, 3, 8, t=2, form=0)
+        for took in (fwd, bwd):
+            assert "kernel:scalar-grouped" in took and not took & {"second-item:grouped", "short-last-group"}, took
+        fwd, bwd = _check(double, dtype, method, 2101, 1, 3, 3, t=1, form=1)
+        for took in (fwd, bwd):
+            assert {"kernel:scalar-grouped", "short-last-group"} <= took and "second-item:grouped" not in took, took
+        fwd, bwd = _check(double, dtype, method, 4200, 512, 1, 2, t=2, form=2)
+        assert {"kernel:scalar-grouped", "second-item:grouped"} <= fwd and "second-pass:single" not in fwd, fwd
+        assert {"kernel:scalar-grouped", "second-item:grouped", "second-pass:backward"} <= bwd, bwd
+
+
+@pytest.mark.parametrize("row", P.TABLE, ids=P.ROW_IDS)
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
+def test_every_launch_plan_equals_the_double_bit_for_bit(dtype, row):
+    """tests/_cde_plans.py's table: the shape takes the branches the row is there for — asserted from the launch plan before anything
+    is launched, forward and backward, and again from the operands launched — and both kernels give the double's bits with both
+    methods.  (The bits do not depend on the plan: the double is the one of the small shapes.)"""
+    (B, H, C), fwd, bwd = P.row_case(row, _DT[dtype])
+    for backward, want in ((False, fwd), (True, bwd)):
+        got = P.features(_query(backward, _DT[dtype], B, H, C, row.misalign), B, H, C, backward)
+        assert want <= got, (row.label, "backward" if backward else "forward", "not taken:", sorted(want - got))
+    double = CdeDoubleBackend()
+    n = P.TABLE.index(row)
+    for k, method in enumerate(("linear", "cubic")):
+        took = _check(double, dtype, method, B, H, C, Tn=(3, 2, 8)[n % 3] if C < 2048 else 3, t=(n + 3 * k) % 8, form=(n + k) % 3,
+                      misalign=row.misalign)
+        assert fwd <= took[0] and bwd <= took[1], (row.label, took)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
+def test_the_suites_shapes_reach_every_reachable_plan(dtype):
+    """Over every shape this module launches at the default settings (the grid of the first test, the three grouped shapes, C = 2050
+    and the plan table), per direction: all six instantiations, a second work item in the LDS, grouped and no-LDS families, a second
+    row pass in the single path, the long path and the backward kernel, a short last slice, a short last group, the streaming loads.
+    A condition, not a measurement: after a retune that moves a shape off its branch this names the branch."""
+    assert P.coverage_gaps(_query, _DT[dtype]) == []
+
+
+def test_a_sliced_launch_beyond_the_grid_in_a_child_process():
+    """The one plan the default settings cannot reach (the slicing keeps B * S within the grid): an 8-workgroup grid and a 4 KiB
+    streaming threshold, read once per process, so in a fresh child (tests/_cde_grid_child.py) — small sliced shapes take second and
+    third work items and the streaming loads; the child asserts that from the plan and compares with the double."""
+    env = dict(os.environ, XDE_GRID_BLOCKS="8", XDE_NT_BYTES="4096")
+    r = subprocess.run([sys.executable, "-m", "tests._cde_grid_child"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    assert "CHILD DONE" in r.stdout, r.stdout[-2000:]
+    assert [line for line in r.stdout.splitlines() if line.startswith("FAIL ")] == []
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
+@pytest.mark.parametrize("method", ["linear", "cubic"])
+def test_times_inside_the_first_and_a_middle_interval_and_outside_the_knots(dtype, method):
+    """The four kinds of time the first test does not ask for (``_times`` 4-7), through all three forms of time, at C below one
+    vector, unaligned, one team and more than one team pass; Tn = 8 (a middle interval), 3 and 2."""
+    double = CdeDoubleBackend()
+    for B, H, C, Tn in ((3, 7, 5, 8), (1, 33, 64, 8), (3, 7, 260, 8), (3, 1, 1, 2), (1, 7, 3, 3), (3, 33, 4, 8)):
+        for t in range(4, 8):
+            for form in range(3):
+                _check(double, dtype, method, B, H, C, Tn, t, form)
+        _check(double, dtype, method, B, H, C, Tn, t=6, form=0, misalign=True)
+        _check(double, dtype, method, B, H, C, Tn, t=7, form=1, misalign=True)
+    assert double.launches.count("cde_contract") == double.launches.count("cde_contract_backward") == 6 * 14
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
+def test_the_autograd_wrapper_at_a_grouped_and_a_two_pass_shape(dtype):
+    """CdeContractFn.apply and its backward (the operands torch's allocator hands out) at the plan table's short-last-group shape and
+    its two-pass shape: the output and the gradient of F are the double's _cde_contract / _cde_contract_backward bit for bit."""
+    be, double, T = _hip.get_backend(), CdeDoubleBackend(), _NPT[dtype]
+    th = torch.from_numpy
+    for (B, H, C), method, fwd, bwd in (((2049, 3, 8), "cubic", "kernel:vec-grouped", "kernel:vec-grouped"),
+                                        ((1024, 70, 64), "linear", "second-pass:single", "second-pass:backward")):
+        rs = np.random.RandomState(B)
+        series, F, gout = rs.randn(B, 8, C).astype(T), rs.randn(B, H, C).astype(T), rs.randn(B, H).astype(T)
+        knots = np.cumsum(0.5 + rs.rand(8)).astype(T)
+        tv = float(knots[3] + 0.5 * (knots[4] - knots[3]))
+        want, gwant = torch.empty(B, H, dtype=dtype), torch.empty(B, H, C, dtype=dtype)
+        double._cde_contract(want, th(F), th(series), th(knots), tv, method)
+        double._cde_contract_backward(gwant, th(gout), th(series), th(knots), tv, method)
+        F_d = th(F).to(DEV).requires_grad_(True)
+        assert fwd in P.features(be._cde_plan(False, F_d, B, H, C), B, H, C, False)
+        out = CdeContractFn.apply(F_d, th(series).to(DEV), th(knots).to(DEV), torch.tensor(tv, dtype=torch.float64, device=DEV), method)
+        out.backward(th(gout).to(DEV))
+        assert bwd in P.features(be._cde_plan(True, F_d.grad, B, H, C), B, H, C, True)
+        assert np.array_equal(out.detach().cpu().numpy(), want.numpy()), (B, H, C)
+        assert np.array_equal(F_d.grad.cpu().numpy(), gwant.numpy()), (B, H, C)
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
@@ -115,7 +223,8 @@ def test_a_row_longer_than_the_on_chip_table(dtype):
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
 @pytest.mark.parametrize("method", ["linear", "cubic"])
 def test_the_identity_field_returns_the_spline_derivative(dtype, method):
-    """H = C and F[b] = I: the output is X.derivative(t), the `der` of xde_history_gather, bit for bit (not through the double)."""
+    """H = C and F[b] = I: the output is X.derivative(t), the `der` of xde_history_gather, bit for bit (not through the double) — at
+    every kind of time of ``_times``, so the convention outside the knots is held to the spline's too."""
     be = _hip.get_backend()
     rs = np.random.RandomState(5)
     for C, Tn in ((1, 2), (3, 3), (5, 8), (64, 8), (260, 8)):
