@@ -216,11 +216,26 @@ CDE_PROTOTYPES = {
     "xde_cde_contract_backward": (_i32, [_vp] * 5 + [_dbl, _i32, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),
     "xde_cde_plan": (_i32, [_i32, _vp, _i64, _i32, _i32, _i32, C.POINTER(XdeCdePlan)]),
 }
+class XdeSeamPlan(C.Structure):
+    """Mirror of xde_seam_plan_t (include/xde_hip_seam.h)."""
+
+    _fields_ = [(name, C.c_int32) for name in ("blocks", "per_lane", "resident", "fits")]
+
+
+# the entry points of include/xde_hip_seam.h (error norm + controller + next first stage combine as one resident launch); bound by
+# load_library() after _bind_cde
+SEAM_PROTOTYPES = {
+    "xde_seam_state_bytes": (_i64, None),
+    "xde_seam_plan": (_i32, [_i64, _i32, C.POINTER(XdeSeamPlan)]),
+    "xde_seam_attempt": (_i32, [_vp, _dbl] + [_vp] * 7 + [_dbl, _i64, _i32, _vp, _vp, _vp, _params, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "xde_seam_expired": (_i32, [_vp, C.POINTER(C.c_int64), _vp]),
+}
 SYMBOLS = tuple(PROTOTYPES)
 BACKPROP_SYMBOLS = tuple(BACKPROP_PROTOTYPES)
 GRID_SYMBOLS = tuple(GRID_PROTOTYPES)
 SDE_SYMBOLS = tuple(SDE_PROTOTYPES)
 CDE_SYMBOLS = tuple(CDE_PROTOTYPES)
+SEAM_SYMBOLS = tuple(SEAM_PROTOTYPES)
 XDE_INTERP_MAX_ROWS = 8
 XDE_INTERP_LINEAR, XDE_INTERP_CUBIC = 0, 1
 XDE_ROW_INTERP, XDE_ROW_COPY_A, XDE_ROW_COPY_B = 0, 1, 2
@@ -252,7 +267,7 @@ _REBUILD = "rebuild it with `python -m paddlexde_amd.csrc.build --force`"
 
 
 def _declare(lib, sym):
-    proto = PROTOTYPES.get(sym) or BACKPROP_PROTOTYPES.get(sym) or GRID_PROTOTYPES.get(sym) or SDE_PROTOTYPES.get(sym) or CDE_PROTOTYPES[sym]
+    proto = PROTOTYPES.get(sym) or BACKPROP_PROTOTYPES.get(sym) or GRID_PROTOTYPES.get(sym) or SDE_PROTOTYPES.get(sym) or CDE_PROTOTYPES.get(sym) or SEAM_PROTOTYPES[sym]
     try:
         fn = getattr(lib, sym)
     except AttributeError:
@@ -298,6 +313,12 @@ def _bind_cde(lib):
         _declare(lib, sym)
 
 
+def _bind_seam(lib):
+    """Declare the entry points of include/xde_hip_seam.h on ``lib`` (after ``_bind``: the ABI check comes first)."""
+    for sym in SEAM_SYMBOLS:
+        _declare(lib, sym)
+
+
 def load_library():
     """dlopen libxde_hip.so and declare prototypes.  Raises if it has not been built, or is not the library this binding speaks to."""
     global _lib
@@ -316,6 +337,7 @@ def load_library():
         _bind_grid(lib)
         _bind_sde(lib)
         _bind_cde(lib)
+        _bind_seam(lib)
         _lib = lib
     return _lib
 
@@ -366,6 +388,7 @@ class HipBackend:
         self._mirror_pool = []  # pinned host mirror rings, reused across solver instances
         self._mirrors = {}  # device ctrl pointer -> _Mirror
         self._work_pool = {}  # (device, state dtype, stream) -> free _Work sets
+        self._seam_states = {}  # device ctrl pointer -> barrier state of xde_seam_attempt (zeroed once; tags only grow)
         self._lag_ws = {}  # (device, L, stream) -> workspace of xde_lag_grad (zeroed once; every launch leaves it re-armed)
         self._tls = threading.local()  # .capturing: this THREAD is recording a hipGraph (its launches do not execute)
         # (the init block can ride the mirror only under the checksummed publish protocol, XDE_CTRL_FLAGS bit 8 — the default)
@@ -923,6 +946,50 @@ class HipBackend:
             return
         rc = self.lib.xde_sde_noise(out.data_ptr(), out.numel(), int(seed), int(k), mode, dt, self._stream(out))
         self._check(rc, "xde_sde_noise")
+
+    # -- the seam between two attempts as one resident launch (include/xde_hip_seam.h) ------------------------------------------------
+    # Private for the reason _interp_rows is: the public methods are the contract tests/_cpu_double.py mirrors.  Only AdaptiveRKSolver
+    # (options["seam"]) calls these.
+    SEAM_SPIN_LIMIT = 4_000_000  # polls of the grid barrier before a workgroup gives up (seconds, not microseconds)
+
+    def _seam_plan(self, n, dtype):
+        """The launch plan of ``_seam_attempt`` for an ``n``-element state of ``dtype`` on the current device, as a dict of
+        xde_seam_plan_t's fields.  Nothing is enqueued."""
+        plan = XdeSeamPlan()
+        self._check(self.lib.xde_seam_plan(int(n), dtype_code(dtype), C.byref(plan)), "xde_seam_plan")
+        return {name: int(getattr(plan, name)) for name, _ in XdeSeamPlan._fields_}
+
+    def _seam_state(self, ctrl):
+        key = ctrl.data_ptr()
+        st = self._seam_states.get(key)
+        if st is None:
+            st = self._seam_states[key] = torch.zeros(int(self.lib.xde_seam_state_bytes()), dtype=torch.uint8, device=ctrl.device)
+            weakref.finalize(ctrl, self._seam_states.pop, key, None)
+        return st
+
+    def _seam_attempt(self, k_last, c_last, e_pre, y0, f0, y1, out, a21, ws, ctrl, params, t_span_dev, step_t_dev, t_stage, *,
+                      y0_alt=None, f0_alt=None):
+        """Error norm of the attempt (e_pre form) + controller + ``out = y0' + f0' (a21 dt')``, the next attempt's first stage input, in
+        ONE launch; (y0', f0') = (y1, k_last) when the controller accepts, the attempt's own (y0, f0) otherwise."""
+        self._require_device(k_last, e_pre, y0, f0, y1, out, ws, ctrl, t_span_dev, t_stage, y0_alt, f0_alt)
+        m = self._mirrors.get(ctrl.data_ptr())
+        rc = self.lib.xde_seam_attempt(k_last.data_ptr(), float(c_last), e_pre.data_ptr(), y0.data_ptr(), _ptr(y0_alt), f0.data_ptr(),
+                                       _ptr(f0_alt), y1.data_ptr(), out.data_ptr(), float(a21), y0.numel(), dtype_code(y0.dtype),
+                                       ws.data_ptr(), self._seam_state(ctrl).data_ptr(), ctrl.data_ptr(), C.byref(params),
+                                       t_span_dev.data_ptr(), _ptr(step_t_dev), t_stage.data_ptr(), m.ptr if m is not None else None,
+                                       self.SEAM_SPIN_LIMIT, self._stream(y0))
+        self._check(rc, "xde_seam_attempt")
+        if m is not None and not self._is_capturing():
+            m.seq += 1
+
+    def _seam_expired(self, ctrl):
+        """Tag (controller launch number) of the first seam launch on ``ctrl`` whose grid barrier expired, 0 = none.  Blocking."""
+        st = self._seam_states.get(ctrl.data_ptr())
+        if st is None:
+            return 0
+        tag = C.c_int64(0)
+        self._check(self.lib.xde_seam_expired(st.data_ptr(), C.byref(tag), self._stream(ctrl)), "xde_seam_expired")
+        return int(tag.value)
 
     # -- cdeint's vector field (include/xde_hip_cde.h) ----------------------------------------------------------------------------------
     # Private for the reason _interp_rows is: the public methods are the contract tests/_cpu_double.py mirrors.  Only CdeContractFn

@@ -48,12 +48,13 @@ class SyncPipeline:
         if cb is not None:
             cb(*args)
 
-    def attempt_and_resolve(self):
-        """One attempted step, its verdict read: ``(base, y1, ks, c)``.  The accepted proposal becomes the new base."""
+    def attempt_and_resolve(self, seam=False):
+        """One attempted step, its verdict read: ``(base, y1, ks, c)``.  The accepted proposal becomes the new base.  ``seam``: another
+        attempt follows for certain, so this one may end in the resident seam launch."""
         s = self.s
         base = s._base
         cb_args = self._callbacks_before(s._last, base) if s._has_callbacks else None
-        y1, ks = s._attempt(base)
+        y1, ks = s._attempt(base, seam=seam)
         s._n_attempts += 1
         c = s.backend.ctrl_read(s._ctrl)  # the step's one host sync
         if s.record_trace:
@@ -71,8 +72,15 @@ class SyncPipeline:
         done = 0
         if stop_on_done is None:
             stop_on_done = max_attempts is None
+        d = s._direction
+        t_last = float(s._t_host[-1])
         while max_attempts is None or done < max_attempts:
-            base, y1, ks, c = self.attempt_and_resolve()
+            # The seam launch writes the NEXT attempt's first stage input: it is taken only where a next attempt is certain — not by
+            # the last attempt of a budget, and, where the solve's end stops the loop, not by an attempt that may end the solve (its
+            # landing point is the newest block's `t_plan`; unknown before the first verdict).
+            seam = s._seam_on and (max_attempts is None or done + 1 < max_attempts) and (
+                not stop_on_done or (c is not None and d * c.t_plan < d * t_last))
+            base, y1, ks, c = self.attempt_and_resolve(seam)
             done += 1
             if c.accept:
                 if c.out_end > c.out_begin and s._solution is not None:
@@ -122,7 +130,14 @@ class LagPipeline:
         while to_end or done < max_attempts:
             base = s._base
             alt = (s._pending[0], s._pending[1][-1]) if s._pending is not None else None
-            y1, ks = s._attempt(base, alt)
+            # The seam launch writes the NEXT attempt's first stage input, so it is taken only where a next attempt is certain: not by
+            # the last attempt of a budget, and in a solve that runs to its end not by an attempt that could end it.  The host does not
+            # know yet where this attempt lands — the newest verdict it has read is the one before the pending attempt's — but it lands
+            # no further than the pending attempt's planned end (`t_plan`) plus the largest step the controller can follow it with
+            # (`ifactor` times the pending step).
+            seam = s._seam_on and (to_end or done + 1 < max_attempts) and (
+                not to_end or (c is not None and d * (c.t_plan + float(s.ifactor) * c.dt) < d * t_last))
+            y1, ks = s._attempt(base, alt, seam=seam)
             s._n_attempts += 1
             done += 1
             if s._solution is not None:

@@ -89,6 +89,7 @@ class AdaptiveRKSolver(NormReductions, AdaptiveSolver):
         _xde_segment_shapes=None,
         _short_solves=False,
         _fused_first_step=True,
+        seam="auto",
         **kwargs,
     ):
         super().__init__(xde=xde, dtype=dtype, y0=y0, **kwargs)
@@ -96,6 +97,8 @@ class AdaptiveRKSolver(NormReductions, AdaptiveSolver):
             raise NotImplementedError("jump_t calls a non-existent self.func in the reference (SURVEY D7)")
         if pipeline not in ("auto", "sync", "lag", "graph"):
             raise ValueError("pipeline must be 'auto', 'sync', 'lag' or 'graph'")
+        if seam not in ("auto", "resident", "launches"):
+            raise ValueError("seam must be 'auto', 'resident' or 'launches'")
         if controller not in ("I", "PI"):
             raise ValueError("controller must be 'I' (reference) or 'PI' (opt-in)")
         if dtype not in (torch.float32, torch.float64):
@@ -119,6 +122,10 @@ class AdaptiveRKSolver(NormReductions, AdaptiveSolver):
         self.step_t = None if step_t is None else np.asarray(torch.as_tensor(step_t).cpu().numpy(), dtype=tt)
         self.jump_t = None
         self.pipeline = pipeline
+        # options["seam"]: how an attempt hands over to the next one.  "launches": error norm, controller and the next attempt's
+        # first stage combine as three launches.  "resident": ONE launch whose workgroups stay resident across a grid barrier
+        # (xde_seam_attempt) wherever the state fits it, else an error.  "auto": "resident" where it was measured faster (_seam_resolve).
+        self._seam = seam
         self.controller = controller
         self.pi_beta = float(pi_beta)
         self.process_group = process_group
@@ -178,6 +185,7 @@ class AdaptiveRKSolver(NormReductions, AdaptiveSolver):
         # attempt.  SINGLE_MAX_ELEMS = largest state (elements) served that way.  (At large sizes one ticketed launch for
         # norm + controller was measured no faster than two — 36.4 us vs 23.1 + 12 us on config 2 — and is not offered.)
         self._single_max = self.SINGLE_MAX_ELEMS
+        self._seam_on = self._carry = False  # (resolved per solve: _setup)
 
         self.backend = _hip.get_backend()
         self.nfe = 0  # calls func has received
@@ -380,7 +388,44 @@ class AdaptiveRKSolver(NormReductions, AdaptiveSolver):
             self._replay_dev = upload(tab, dev)  # kept alive by the solver: params hold its raw pointer
             p.replay, p.n_replay = self._replay_dev.data_ptr(), len(self._replay)
         self._params = p
+        self._seam_on = self._seam_resolve()
+        self._carry = False  # the pending attempt's first stage input and stage times were written by the last seam launch
         return t_span
+
+    # smallest state (elements) "auto" hands to the resident launch: the headline size, where the A/B met its bar; at 2^22 elements
+    # (config 4's shard) every block was faster too, but by less than the spread asked for
+    SEAM_AUTO_MIN_ELEMS = 1 << 23
+
+    def _seam_resolve(self):
+        """Whether this solve's attempts end in the resident seam launch (options["seam"])."""
+        if self._seam == "launches":
+            return False
+        y0 = self.y0
+        n = y0.numel()
+        why = None
+        if self.process_group is not None:
+            why = "a process_group"
+        elif self._custom_norm or self._chunks is not None or len(self._norm_segs) != 1 or self._segs != [(0, n)]:
+            why = "a custom norm or a state of several segments"
+        elif not (self._fsal and self._fuse_err) or 0 in self._presum or 1 in self._presum or self._stage_plan[0][0] != [0]:
+            why = "a pair without FSAL and a fused error estimate"
+        elif self._replay or self.pipeline == "graph":
+            why = "a prescribed step sequence or the graph pipeline's captured attempt"
+        elif n < 1:
+            why = "an empty state"
+        if why is None and self._seam == "auto" and (not y0.is_cuda or self._small_state or n < self.SEAM_AUTO_MIN_ELEMS):
+            return False
+        plan = None
+        if why is None:
+            plan = self.backend._seam_plan(n, y0.dtype)  # the fit is computed from the launch's grid and the proven residency
+            if not plan["fits"]:
+                why = "a state that does not fit the resident launch ({blocks} workgroups, {resident} resident; {per_lane} vectors " \
+                      "per lane)".format(**plan)
+        if why is not None:
+            if self._seam == "resident":
+                raise ValueError("options['seam'] = 'resident' cannot serve " + why)
+            return False
+        return True
 
     def _after_integrate(self):
         w, self._work = getattr(self, "_work", None), None
@@ -461,7 +506,8 @@ class AdaptiveRKSolver(NormReductions, AdaptiveSolver):
     # ------------------------------------------------------------------------------------------
     # one attempted step = _runge_kutta_step (:129-181) + error ratio + controller (:183-284)
     # ------------------------------------------------------------------------------------------
-    def _attempt(self, base, alt=None):
+    def _attempt(self, base, alt=None, seam=False):
+        """``seam``: end in the resident seam launch (the caller enqueues another attempt on the same candidates next)."""
         be = self.backend
         ctrl = self._ctrl
         y0, f0 = base
@@ -471,7 +517,15 @@ class AdaptiveRKSolver(NormReductions, AdaptiveSolver):
         y_stage = None
         live = {storage_ptr(x) for x in ([y0, f0] + ([y0_alt, k0_alt] if alt is not None else []))}
         fuse = self._fuse_err and not self._custom_norm
-        for i in range(S):
+        first = 0
+        if self._carry:
+            # the previous attempt's seam launch has written this attempt's first stage input (and the stage times)
+            self._carry = False
+            first = 1
+            ks.append(self._eval(self._t_views[0], self._scratch, live=live))
+            live.add(storage_ptr(ks[-1]))
+            y_stage = self._scratch
+        for i in range(first, S):
             idx, coef = self._stage_plan[i]
             out = torch.empty_like(y0) if (i == S - 1 and self._fsal) else self._scratch
             pre = self._presum.get(i)
@@ -523,6 +577,11 @@ class AdaptiveRKSolver(NormReductions, AdaptiveSolver):
             self._reduce_chunks(partial, self._csums[0:1], nonfinite_out=self._csums[m : m + 1])
             be.rk_control(ctrl, self._params, None, self._csums, self._t_span_dev, self._step_t_dev, self._t_stage)
             return y1, ks
+        if seam and self._seam_on:
+            be._seam_attempt(ks[-1], coef[-1], self._ebuf, y0, f0, y1, self._scratch, self._stage_plan[0][1][0], self._ws, ctrl,
+                             self._params, self._t_span_dev, self._step_t_dev, self._t_stage, y0_alt=y0_alt, f0_alt=k0_alt)
+            self._carry = True
+            return y1, ks
         if self.process_group is None and self._small_state:
             # single GPU, small state: error norm + controller in ONE one-workgroup launch
             if fuse:
@@ -561,6 +620,7 @@ class AdaptiveRKSolver(NormReductions, AdaptiveSolver):
         if c.status == _hip.STATUS_DT_UNDERFLOW:
             raise AssertionError(_STATUS_MSG[c.status].format(c.dt))
         if c.status == _hip.STATUS_NONFINITE:
+            self._raise_seam_expired()
             if self.norm_exchange is not None and self.norm_exchange.error():
                 q, by = self.norm_exchange.error_info()
                 raise _hip.XdeError("peer-to-peer norm exchange {} timed out{}: a rank of the process group did not arrive "
@@ -573,6 +633,13 @@ class AdaptiveRKSolver(NormReductions, AdaptiveSolver):
         if c.status == _hip.STATUS_MAX_STEPS:
             raise AssertionError(_STATUS_MSG[c.status].format(c.steps_in_interval, self.max_num_steps))
         raise AssertionError("solver status {}".format(c.status))
+
+    def _raise_seam_expired(self):
+        tag = self.backend._seam_expired(self._ctrl) if self._seam_on else 0
+        if tag:
+            raise _hip.XdeError("the grid barrier of the resident seam launch (controller launch {}) expired: a workgroup was not "
+                                "resident in time (the device is shared or over-subscribed); options['seam'] = 'launches' takes the "
+                                "separate launches".format(tag))
 
     def _finish(self, c, base):
         self.stats = {
@@ -601,6 +668,7 @@ class AdaptiveRKSolver(NormReductions, AdaptiveSolver):
         self._pending = None  # lag pipeline: (y1, [f1], read handle) of the newest, unresolved attempt
         self._n_attempts = 0
         self._last = None
+        self._carry = False
         self._graph_pl.reset()
 
     # (names other modules know these by: bench.py's settle loop, the tests' policy assertions)
@@ -619,6 +687,10 @@ class AdaptiveRKSolver(NormReductions, AdaptiveSolver):
         pipeline = {"auto": self._auto, "lag": self._lag, "graph": self._graph_pl, "sync": self._sync}[self.pipeline]
         with torch.no_grad():  # once per advance, not once per func evaluation
             c = pipeline.advance(max_attempts)
+        if self._seam_on:
+            # a workgroup that gave up on the barrier has stopped the solve at the next seam launch; the last attempt of an advance
+            # has none after it, so the word is read here too
+            self._raise_seam_expired()
         self._finish(c, self._base)
         return c
 
