@@ -7,7 +7,11 @@ knots are the unit grid); ``z0 = initial(X.evaluate(t0))``, ``dz = f_theta(z) dX
 linear read-out of ``z`` at the last time gives the logit (loss: binary cross-entropy).  Trained through ``cdeint`` with RK4 on the
 knots (gradients through the steps), or with ``--adjoint`` through ``cdeint_adjoint`` with Dopri5 (the continuous adjoint).
 
-    python examples/cde_demo.py --max-steps 60 [--adjoint]
+``--control natural`` drives the model with ``NaturalCubicSpline`` instead: the C2 natural cubic spline through the observed points, on
+the series' own times.  With it ``--irregular`` samples the spirals at times drawn from the seed (not ``linspace``) and ``--missing P``
+sets a share ``P`` of the x / y entries to NaN ("not observed"), also from the seed.
+
+    python examples/cde_demo.py --max-steps 60 [--adjoint] [--control natural [--irregular] [--missing 0.3]]
 """
 import argparse
 import math
@@ -21,22 +25,33 @@ import torch.nn as nn
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from paddlexde_amd.functional import cdeint, cdeint_adjoint  # noqa: E402
-from paddlexde_amd.interpolation import CubicHermiteSpline  # noqa: E402
+from paddlexde_amd.interpolation import CubicHermiteSpline, NaturalCubicSpline  # noqa: E402
 from paddlexde_amd.solver import RK4, Dopri5  # noqa: E402
 
 CHANNELS = 3  # (time, x, y)
 
 
-def make_data(n=128, length=32, seed=0, device="cuda:0"):
-    """series [n, length, 3] and labels [n] (1: clockwise)."""
+def make_data(n=128, length=32, seed=0, device="cuda:0", irregular=False, missing=0.0):
+    """series [n, length, 3] and labels [n] (1: clockwise).  ``irregular``: the sample times are drawn from the seed (the ends stay 0
+    and 4 pi); ``missing``: that share of the x / y entries after the first row is NaN, drawn from the seed."""
     gen = torch.Generator().manual_seed(seed)
     t = torch.linspace(0.0, 4.0 * math.pi, length)
+    extra = torch.Generator().manual_seed(seed + 1)  # (its own stream: the draws below are the same with and without the options)
+    if irregular:
+        # each interior time moves up to 0.4 of a grid step either way: spacings between 0.2 and 1.8 steps
+        jitter = 0.8 * (torch.rand(length - 2, generator=extra) - 0.5)
+        t = t + (4.0 * math.pi / (length - 1)) * torch.cat([torch.zeros(1), jitter, torch.zeros(1)])
     phase = 2.0 * math.pi * torch.rand(n, 1, generator=gen)
     labels = (torch.arange(n) % 2).float()
     sign = (1.0 - 2.0 * labels)[:, None]  # anticlockwise: +1, clockwise: -1
     r = 1.0 / (1.0 + 0.2 * t)[None, :]
     x = r * torch.cos(phase + sign * t[None, :]) + 0.01 * torch.randn(n, length, generator=gen)
     y = r * torch.sin(phase + sign * t[None, :]) + 0.01 * torch.randn(n, length, generator=gen)
+    if missing > 0.0:
+        gone = torch.rand(n, length, 2, generator=extra) < missing
+        gone[:, 0, :] = False  # (every column keeps an observed value)
+        x = x.masked_fill(gone[..., 0], float("nan"))
+        y = y.masked_fill(gone[..., 1], float("nan"))
     series = torch.stack([t[None, :].expand(n, -1), x, y], dim=-1)
     return series.to(device), labels.to(device)
 
@@ -69,10 +84,16 @@ class NeuralCDE(nn.Module):
         return self.readout(zT)[:, 0]
 
 
-def train(max_steps=60, n=128, length=32, hidden=8, seed=0, device="cuda:0", adjoint=False, log_every=10):
+def train(max_steps=60, n=128, length=32, hidden=8, seed=0, device="cuda:0", adjoint=False, log_every=10, control="cubic", irregular=False,
+          missing=0.0):
+    if control not in ("cubic", "natural"):
+        raise ValueError("control must be 'cubic' or 'natural', got {!r}".format(control))
+    if control == "cubic" and (irregular or missing > 0.0):
+        raise ValueError("irregular times and missing values need control='natural': CubicHermiteSpline keeps the reference's "
+                         "uniform-grid conventions and has no notion of an unobserved entry")
     torch.manual_seed(seed)
-    series, labels = make_data(n, length, seed, device)
-    X = CubicHermiteSpline(series)
+    series, labels = make_data(n, length, seed, device, irregular, missing)
+    X = CubicHermiteSpline(series) if control == "cubic" else NaturalCubicSpline(series, series[0, :, 0])  # (channel 0 is the time)
     model = NeuralCDE(hidden).to(device)
     opt = torch.optim.Adam(model.parameters(), lr=1e-2)
     losses = []
@@ -95,6 +116,9 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--max-steps", type=int, default=60)
     ap.add_argument("--adjoint", action="store_true", help="train through cdeint_adjoint (Dopri5) instead of cdeint (RK4)")
+    ap.add_argument("--control", choices=("cubic", "natural"), default="cubic", help="the control path through the series")
+    ap.add_argument("--irregular", action="store_true", help="sample times drawn from the seed (needs --control natural)")
+    ap.add_argument("--missing", type=float, default=0.0, metavar="P", help="share of x / y entries set to NaN (needs --control natural)")
     a = ap.parse_args()
-    ls = train(a.max_steps, adjoint=a.adjoint)
+    ls = train(a.max_steps, adjoint=a.adjoint, control=a.control, irregular=a.irregular, missing=a.missing)
     print("first loss {:.4f} -> last loss {:.4f}".format(ls[0], ls[-1]))

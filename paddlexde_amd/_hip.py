@@ -230,12 +230,21 @@ SEAM_PROTOTYPES = {
     "xde_seam_attempt": (_i32, [_vp, _dbl] + [_vp] * 7 + [_dbl, _i64, _i32, _vp, _vp, _vp, _params, _vp, _vp, _vp, _vp, _i64, _vp]),
     "xde_seam_expired": (_i32, [_vp, C.POINTER(C.c_int64), _vp]),
 }
+# the entry points of include/xde_hip_spline.h (the natural cubic spline control: coefficient build, gather, and the two contraction
+# launches on it); bound by load_library() after _bind_seam
+SPLINE_PROTOTYPES = {
+    "xde_spline_natural_coeffs": (_i32, [_vp] * 4 + [_i64, _i32, _i32, _i32, _vp]),
+    "xde_spline_natural_gather": (_i32, [_vp] * 6 + [_i64, _i32, _i32, _i32, _i32, _vp]),
+    "xde_cde_contract_natural": (_i32, [_vp] * 6 + [_dbl, _i32, _i64, _i32, _i32, _i32, _i32, _vp]),
+    "xde_cde_contract_natural_backward": (_i32, [_vp] * 6 + [_dbl, _i32, _i64, _i32, _i32, _i32, _i32, _vp]),
+}
 SYMBOLS = tuple(PROTOTYPES)
 BACKPROP_SYMBOLS = tuple(BACKPROP_PROTOTYPES)
 GRID_SYMBOLS = tuple(GRID_PROTOTYPES)
 SDE_SYMBOLS = tuple(SDE_PROTOTYPES)
 CDE_SYMBOLS = tuple(CDE_PROTOTYPES)
 SEAM_SYMBOLS = tuple(SEAM_PROTOTYPES)
+SPLINE_SYMBOLS = tuple(SPLINE_PROTOTYPES)
 XDE_INTERP_MAX_ROWS = 8
 XDE_INTERP_LINEAR, XDE_INTERP_CUBIC = 0, 1
 XDE_ROW_INTERP, XDE_ROW_COPY_A, XDE_ROW_COPY_B = 0, 1, 2
@@ -267,7 +276,7 @@ _REBUILD = "rebuild it with `python -m paddlexde_amd.csrc.build --force`"
 
 
 def _declare(lib, sym):
-    proto = PROTOTYPES.get(sym) or BACKPROP_PROTOTYPES.get(sym) or GRID_PROTOTYPES.get(sym) or SDE_PROTOTYPES.get(sym) or CDE_PROTOTYPES.get(sym) or SEAM_PROTOTYPES[sym]
+    proto = PROTOTYPES.get(sym) or BACKPROP_PROTOTYPES.get(sym) or GRID_PROTOTYPES.get(sym) or SDE_PROTOTYPES.get(sym) or CDE_PROTOTYPES.get(sym) or SEAM_PROTOTYPES.get(sym) or SPLINE_PROTOTYPES[sym]
     try:
         fn = getattr(lib, sym)
     except AttributeError:
@@ -319,6 +328,12 @@ def _bind_seam(lib):
         _declare(lib, sym)
 
 
+def _bind_spline(lib):
+    """Declare the entry points of include/xde_hip_spline.h on ``lib`` (after ``_bind``: the ABI check comes first)."""
+    for sym in SPLINE_SYMBOLS:
+        _declare(lib, sym)
+
+
 def load_library():
     """dlopen libxde_hip.so and declare prototypes.  Raises if it has not been built, or is not the library this binding speaks to."""
     global _lib
@@ -338,6 +353,7 @@ def load_library():
         _bind_sde(lib)
         _bind_cde(lib)
         _bind_seam(lib)
+        _bind_spline(lib)
         _lib = lib
     return _lib
 
@@ -1038,6 +1054,74 @@ class HipBackend:
         rc = self.lib.xde_cde_plan(int(bool(backward)), big.data_ptr(), int(B), int(H), int(channels), dtype_code(big.dtype), C.byref(plan))
         self._check(rc, "xde_cde_plan")
         return {name: int(getattr(plan, name)) for name, _ in XdeCdePlan._fields_}
+
+    # -- the natural cubic spline control (include/xde_hip_spline.h) -------------------------------------------------------------------
+    # Private for the reason the _cde_* methods are.  NaturalCubicSpline (interpolation) and CdeContractFn (xde/base_cde.py) call these.
+    def _spline_operands(self, who, *tensors):
+        self._require_device(*tensors)
+        first = tensors[0]
+        for x in tensors:
+            if not x.is_contiguous() or x.dtype != first.dtype or x.device != first.device:
+                raise XdeError("{}: the operands must be contiguous tensors of one dtype on one device".format(who))
+
+    def _spline_natural_coeffs(self, Y, M, series, knots):
+        """``Y, M [B, Tn, C]`` of the natural cubic spline through the observed (non-NaN) entries of ``series [B, Tn, C]`` over
+        ``knots [Tn]``: the end rule, the Thomas solve and the fill of include/xde_hip_spline.h.  One launch."""
+        who = "_spline_natural_coeffs"
+        self._spline_operands(who, Y, M, series, knots)
+        if series.dim() != 3 or Y.shape != series.shape or M.shape != series.shape or tuple(knots.shape) != (series.shape[1],):
+            raise XdeError("{}: expected series, Y, M [B, Tn, C] and knots [Tn], got {}, {}, {}, {}".format(
+                who, tuple(series.shape), tuple(Y.shape), tuple(M.shape), tuple(knots.shape)))
+        B, Tn, C_ = series.shape
+        rc = self.lib.xde_spline_natural_coeffs(Y.data_ptr(), M.data_ptr(), series.data_ptr(), knots.data_ptr(), B, Tn, C_,
+                                                dtype_code(series.dtype), self._stream(series))
+        self._check(rc, "xde_spline_natural_coeffs")
+
+    def _spline_natural_gather(self, val, der, Y, M, knots, tq):
+        """``val, der [..., L, D]`` of the path ``(Y, M [..., Tn, D], knots [Tn])`` at the query times ``tq [L]`` (``der`` may be
+        None): history_gather's layout, the bits the contraction builds dX from."""
+        who = "_spline_natural_gather"
+        self._spline_operands(who, *[x for x in (val, der, Y, M, knots, tq) if x is not None])
+        if val.numel() == 0:
+            return
+        Tn, D = Y.shape[-2], Y.shape[-1]
+        if M.shape != Y.shape or tuple(knots.shape) != (Tn,) or tuple(val.shape) != tuple(Y.shape[:-2]) + (tq.numel(), D) or (
+                der is not None and der.shape != val.shape):
+            raise XdeError("{}: shapes do not agree: Y {}, M {}, knots {}, tq {}, val {}".format(
+                who, tuple(Y.shape), tuple(M.shape), tuple(knots.shape), tuple(tq.shape), tuple(val.shape)))
+        rc = self.lib.xde_spline_natural_gather(val.data_ptr(), _ptr(der), Y.data_ptr(), M.data_ptr(), knots.data_ptr(), tq.data_ptr(),
+                                                Y.numel() // (Tn * D), Tn, tq.numel(), D, dtype_code(Y.dtype), self._stream(Y))
+        self._check(rc, "xde_spline_natural_gather")
+
+    def _cde_natural_call(self, who, out, src, Y, M, knots, t):
+        big, small = (src, out) if who == "_cde_contract_natural" else (out, src)
+        self._spline_operands(who, out, src, Y, M, knots)
+        if Y.dim() != 3 or big.dim() != 3 or small.dim() != 2:
+            raise XdeError("{}: expected Y, M [B, Tn, C], F [B, H, C] and out [B, H]".format(who))
+        B, Tn, C_ = Y.shape
+        H = big.shape[1]
+        if tuple(big.shape) != (B, H, C_) or tuple(small.shape) != (B, H) or tuple(knots.shape) != (Tn,) or M.shape != Y.shape:
+            raise XdeError("{}: shapes do not agree: Y {}, M {}, knots {}, F {}, out {}".format(
+                who, tuple(Y.shape), tuple(M.shape), tuple(knots.shape), tuple(big.shape), tuple(small.shape)))
+        if torch.is_tensor(t):
+            self._require_device(t)
+            if t.numel() != 1 or t.dtype not in (torch.float32, torch.float64) or t.device != Y.device:
+                raise XdeError("{}: t must be ONE float32 / float64 element on the series' device (got shape {}, {}, {})".format(
+                    who, tuple(t.shape), t.dtype, t.device))
+            t_dev, t_host, tt = t.data_ptr(), 0.0, dtype_code(t.dtype)
+        else:
+            t_dev, t_host, tt = None, float(t), XDE_F64
+        rc = getattr(self.lib, "xde" + who)(out.data_ptr(), src.data_ptr(), Y.data_ptr(), M.data_ptr(), knots.data_ptr(), t_dev, t_host, tt,
+                                            B, H, C_, Tn, dtype_code(Y.dtype), self._stream(Y))
+        self._check(rc, "xde" + who)
+
+    def _cde_contract_natural(self, out, F, Y, M, knots, t):
+        """``_cde_contract`` with ``dX`` the derivative at ``t`` of the natural cubic spline ``(Y, M, knots)``.  One launch."""
+        self._cde_natural_call("_cde_contract_natural", out, F, Y, M, knots, t)
+
+    def _cde_contract_natural_backward(self, gF, gout, Y, M, knots, t):
+        """``gF[b, h, c] = gout[b, h] * dX[b, c]``: the cotangent of ``_cde_contract_natural``'s F.  One launch."""
+        self._cde_natural_call("_cde_contract_natural_backward", gF, gout, Y, M, knots, t)
 
     def hermite_gather(self, val, der, his, his_t, lags):
         """his [..., T, D] (contiguous), his_t [T], lags [L]  ->  val, der [..., L, D]."""

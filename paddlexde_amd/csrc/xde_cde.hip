@@ -3,6 +3,8 @@
 //   xde_cde_contract            out[b, h]   = sum_c F[b, h, c] * dX[b, c]
 //   xde_cde_contract_backward   gF[b, h, c] = gout[b, h] * dX[b, c]
 //
+//   xde_cde_contract_natural / _backward   the same two on the natural cubic spline (Y, M) of include/xde_hip_spline.h: dX from four rows
+//
 // dX[b, :] is the time derivative of the control spline through series[b] at the launch's time: the `der` of xde_history_gather for
 // one query, from the same device functions (xde_spline_device.hpp), kept in LDS / registers and never written out.  F (or gF) is the
 // only large operand and crosses HBM once, in 16-byte vectors; as framework ops this was a spline launch (value AND derivative
@@ -13,6 +15,7 @@
 // the summation order inside a team is the header's, whatever the grid, the slicing or the alignment.
 
 #include "xde_hip_cde.h"
+#include "xde_hip_spline.h"
 
 #include "xde_common.hpp"
 #include "xde_spline_device.hpp"
@@ -23,11 +26,13 @@ namespace {
 
 constexpr int kCdeMaxC = 2048;  // channels of dX[b, :] a workgroup keeps in LDS (16 KiB of fp64); a longer row is recomputed per use
 constexpr int kCdeRows = 4;     // rows of F a team has in flight (independent 16-byte loads per lane)
+constexpr int kCdeNatural = 3;  // CdeArgs::method of the natural control (xde_hip_spline.h); the XDE_HISTORY_* codes are 0..2
 
 struct CdeArgs {
   void* out;         // out[B, H]   | gF[B, H, C]
   const void* in;    // F[B, H, C]  | gout[B, H]
-  const void* series;
+  const void* series;  // natural control: Y
+  const void* coef;    // natural control: M (else `series` again, never read)
   const void* knots;
   const void* t_dev;
   double t_host;
@@ -42,21 +47,28 @@ struct CdeArgs {
   int nt;        // stream F (it is read once, and larger than the caches)
 };
 
-template <typename T>
+// (NAT: the natural control, an instantiation of its own — the linear / cubic ones carry none of its code or registers)
+template <typename T, bool NAT>
 struct CdeTab {
   RowsLag<T> lin;
   RowsScale<T> sc;
   HermiteLag<T> cub;
 };
+template <typename T>
+struct CdeTab<T, true> {
+  NaturalLag<T> nat;
+};
 
 // the launch's time -> the query's table entry (one thread per workgroup)
-template <typename T>
-__device__ __forceinline__ void cde_make_tab(CdeTab<T>* tb, const CdeArgs& a) {
+template <typename T, bool NAT>
+__device__ __forceinline__ void cde_make_tab(CdeTab<T, NAT>* tb, const CdeArgs& a) {
   double t = a.t_host;
   if (a.t_dev) t = a.time_f64 ? *static_cast<const double*>(a.t_dev) : double(*static_cast<const float*>(a.t_dev));
   const T tau = T(t);  // the time in the series dtype first (InterpolationBase._gather)
   const T* ts = static_cast<const T*>(a.knots);
-  if (a.method == XDE_HISTORY_LINEAR) {
+  if constexpr (NAT) {
+    tb->nat = make_natural_lag<T>(ts, tau, a.Tn);
+  } else if (a.method == XDE_HISTORY_LINEAR) {
     tb->lin = make_lag<T, 2>(ts, tau, a.Tn);
     tb->sc = make_scales<T, 2>(ts, tb->lin.row[0], a.Tn);
   } else {
@@ -64,11 +76,15 @@ __device__ __forceinline__ void cde_make_tab(CdeTab<T>* tb, const CdeArgs& a) {
   }
 }
 
-// dX[b, c]: `sb` = series[b]
-template <typename T>
-__device__ __forceinline__ T cde_dx(const CdeTab<T>& tb, int method, const T* __restrict__ sb, int c, int C, int Tn) {
+// dX[b, c]: `sb` = series[b], `mb` = coef[b]
+template <typename T, bool NAT>
+__device__ __forceinline__ T cde_dx(const CdeTab<T, NAT>& tb, int method, const T* __restrict__ sb, const T* __restrict__ mb, int c, int C,
+                                    int Tn) {
   T val, der;
-  if (method == XDE_HISTORY_LINEAR) {
+  if constexpr (NAT) {
+    const int64_t at = int64_t(tb.nat.i) * C + c;  // (i <= Tn - 2: row i + 1 exists)
+    natural_eval<T>(tb.nat, sb[at], sb[at + C], mb[at], mb[at + C], val, der);
+  } else if (method == XDE_HISTORY_LINEAR) {
     const T x[2] = {sb[int64_t(tb.lin.row[0]) * C + c], sb[int64_t(tb.lin.row[1]) * C + c]};
     rows_eval<T, 2>(tb.lin, tb.sc, x, val, der);
   } else {
@@ -79,17 +95,17 @@ __device__ __forceinline__ T cde_dx(const CdeTab<T>& tb, int method, const T* __
 }
 
 // s_dx[g C + c] <- dX[b0 + g, c], g < nb  (between two barriers: the previous item's readers are done, this item's readers see it);
-// `sb` = series[b0]
-template <typename T>
-__device__ __forceinline__ void cde_fill_dx(T* s_dx, const CdeTab<T>& tb, int method, const T* __restrict__ sb, int nb, int C, int Tn,
-                                            bool first) {
+// `sb` = series[b0], `mb` = coef[b0]
+template <typename T, bool NAT>
+__device__ __forceinline__ void cde_fill_dx(T* s_dx, const CdeTab<T, NAT>& tb, int method, const T* __restrict__ sb, const T* __restrict__ mb,
+                                            int nb, int C, int Tn, bool first) {
   if (!first) __syncthreads();
   if (nb == 1) {
-    for (int c = threadIdx.x; c < C; c += kBlock) s_dx[c] = cde_dx<T>(tb, method, sb, c, C, Tn);
+    for (int c = threadIdx.x; c < C; c += kBlock) s_dx[c] = cde_dx<T, NAT>(tb, method, sb, mb, c, C, Tn);
   } else {
     for (int e = threadIdx.x; e < nb * C; e += kBlock) {
       const int g = e / C;
-      s_dx[e] = cde_dx<T>(tb, method, sb + int64_t(g) * Tn * C, e - g * C, C, Tn);
+      s_dx[e] = cde_dx<T, NAT>(tb, method, sb + int64_t(g) * Tn * C, mb + int64_t(g) * Tn * C, e - g * C, C, Tn);
     }
   }
   __syncthreads();
@@ -136,16 +152,17 @@ __device__ __forceinline__ void cde_load(T* x, const T* __restrict__ F, int64_t 
   }
 }
 
-template <typename T, bool VEC, bool LDSDX, bool GRP>
+template <typename T, bool VEC, bool LDSDX, bool GRP, bool NAT>
 __global__ __launch_bounds__(kBlock) void xde_cde_contract_kernel(CdeArgs a) {
   constexpr int W = VecOf<T>::W;
   constexpr int U = kCdeRows;
-  __shared__ CdeTab<T> tb;
+  __shared__ CdeTab<T, NAT> tb;
   __shared__ T s_dx[LDSDX ? kCdeMaxC : 1];
-  if (threadIdx.x == 0) cde_make_tab<T>(&tb, a);
+  if (threadIdx.x == 0) cde_make_tab<T, NAT>(&tb, a);
   __syncthreads();
   const T* __restrict__ F = static_cast<const T*>(a.in);
   const T* __restrict__ series = static_cast<const T*>(a.series);
+  const T* __restrict__ coef = static_cast<const T*>(a.coef);
   T* __restrict__ out = static_cast<T*>(a.out);
   const int C = a.C, H = a.H, Tn = a.Tn, R = a.R, method = a.method;
   const int NV = (C + W - 1) / W;
@@ -158,6 +175,7 @@ __global__ __launch_bounds__(kBlock) void xde_cde_contract_kernel(CdeArgs a) {
     const CdeItem w = cde_item(a, it);
     const int r1 = w.r1;
     const T* __restrict__ sb = series + w.b0 * int64_t(Tn) * C;
+    const T* __restrict__ mb = NAT ? coef + w.b0 * int64_t(Tn) * C : sb;
     const int64_t row0 = w.b0 * H;
     if (single) {
       // the first rows of F are requested BEFORE dX is built: they do not depend on it
@@ -170,7 +188,7 @@ __global__ __launch_bounds__(kBlock) void xde_cde_contract_kernel(CdeArgs a) {
         }
       };
       load_rows(w.r0);
-      if (LDSDX) cde_fill_dx<T>(s_dx, tb, method, sb, GRP ? w.nb : 1, C, Tn, first);
+      if (LDSDX) cde_fill_dx<T, NAT>(s_dx, tb, method, sb, mb, GRP ? w.nb : 1, C, Tn, first);
       // this lane's channels of dX, per row slot (slots of a grouped item may sit in different batch rows; a grouped item is one pass)
       T dx[U][W];
 #pragma unroll
@@ -180,7 +198,7 @@ __global__ __launch_bounds__(kBlock) void xde_cde_contract_kernel(CdeArgs a) {
 #pragma unroll
         for (int k = 0; k < W; ++k) {
           const int c = j * W + k;
-          dx[u][k] = c < C ? (LDSDX ? s_dx[g * C + c] : cde_dx<T>(tb, method, sb + int64_t(g) * Tn * C, c, C, Tn)) : T(0);
+          dx[u][k] = c < C ? (LDSDX ? s_dx[g * C + c] : cde_dx<T, NAT>(tb, method, sb + int64_t(g) * Tn * C, mb + int64_t(g) * Tn * C, c, C, Tn)) : T(0);
         }
       }
       for (int rb = w.r0;;) {
@@ -202,7 +220,7 @@ __global__ __launch_bounds__(kBlock) void xde_cde_contract_kernel(CdeArgs a) {
       }
     } else {
       // (rows longer than a team's reach are not grouped: nb == 1)
-      if (LDSDX) cde_fill_dx<T>(s_dx, tb, method, sb, 1, C, Tn, first);
+      if (LDSDX) cde_fill_dx<T, NAT>(s_dx, tb, method, sb, mb, 1, C, Tn, first);
       for (int rb = w.r0; rb < r1; rb += TPB) {
         const int r = rb + team;
         T v = T(0);
@@ -213,7 +231,7 @@ __global__ __launch_bounds__(kBlock) void xde_cde_contract_kernel(CdeArgs a) {
 #pragma unroll
             for (int k = 0; k < W; ++k) {
               const int c = q * W + k;
-              if (VEC || c < C) v = v + x[k] * (LDSDX ? s_dx[c] : cde_dx<T>(tb, method, sb, c, C, Tn));
+              if (VEC || c < C) v = v + x[k] * (LDSDX ? s_dx[c] : cde_dx<T, NAT>(tb, method, sb, mb, c, C, Tn));
             }
           }
         }
@@ -224,16 +242,17 @@ __global__ __launch_bounds__(kBlock) void xde_cde_contract_kernel(CdeArgs a) {
   }
 }
 
-template <typename T, bool VEC, bool LDSDX, bool GRP>
+template <typename T, bool VEC, bool LDSDX, bool GRP, bool NAT>
 __global__ __launch_bounds__(kBlock) void xde_cde_backward_kernel(CdeArgs a) {
   using P = Pack<T, VEC>;
   constexpr int W = P::W;
-  __shared__ CdeTab<T> tb;
+  __shared__ CdeTab<T, NAT> tb;
   __shared__ T s_dx[LDSDX ? kCdeMaxC : 1];
-  if (threadIdx.x == 0) cde_make_tab<T>(&tb, a);
+  if (threadIdx.x == 0) cde_make_tab<T, NAT>(&tb, a);
   __syncthreads();
   const T* __restrict__ gout = static_cast<const T*>(a.in);
   const T* __restrict__ series = static_cast<const T*>(a.series);
+  const T* __restrict__ coef = static_cast<const T*>(a.coef);
   T* __restrict__ gF = static_cast<T*>(a.out);
   const int C = a.C, H = a.H, Tn = a.Tn, method = a.method;
   const int per = C / W;  // vectors (VEC: C % W == 0) or elements (W == 1) of a row
@@ -246,7 +265,8 @@ __global__ __launch_bounds__(kBlock) void xde_cde_backward_kernel(CdeArgs a) {
   for (int64_t it = blockIdx.x; it < items; it += gridDim.x, first = false) {
     const CdeItem w = cde_item(a, it);
     const T* __restrict__ sb = series + w.b0 * int64_t(Tn) * C;
-    if (LDSDX) cde_fill_dx<T>(s_dx, tb, method, sb, GRP ? w.nb : 1, C, Tn, first);
+    const T* __restrict__ mb = NAT ? coef + w.b0 * int64_t(Tn) * C : sb;
+    if (LDSDX) cde_fill_dx<T, NAT>(s_dx, tb, method, sb, mb, GRP ? w.nb : 1, C, Tn, first);
     if (my_row >= rows_per_pass) continue;  // (no barrier below this point of the item)
     for (int r = w.r0 + my_row; r < w.r1; r += rows_per_pass) {
       const int64_t row = w.b0 * H + r;
@@ -257,7 +277,7 @@ __global__ __launch_bounds__(kBlock) void xde_cde_backward_kernel(CdeArgs a) {
 #pragma unroll
         for (int k = 0; k < W; ++k) {
           const int c = q * W + k;
-          o.v[k] = gv * (LDSDX ? s_dx[g * C + c] : cde_dx<T>(tb, method, sb + int64_t(g) * Tn * C, c, C, Tn));
+          o.v[k] = gv * (LDSDX ? s_dx[g * C + c] : cde_dx<T, NAT>(tb, method, sb + int64_t(g) * Tn * C, mb + int64_t(g) * Tn * C, c, C, Tn));
         }
         o.store(gF, row * per + q);
       }
@@ -271,9 +291,10 @@ int pow2ceil(int x) {
   return r;
 }
 
-int cde_check(const std::string& who, const void* out, const void* in, const void* series, const void* knots, const void* t_dev,
-              int time_dtype, int64_t B, int H, int C, int Tn, int method, int dtype) {
-  if (!out || !in || !series || !knots) return fail(XDE_EBADARG, who + ": null pointer");
+// (`coef`: M of the natural control, method kCdeNatural — the public method codes are checked for the other entry points; else `series`)
+int cde_check(const std::string& who, const void* out, const void* in, const void* series, const void* coef, const void* knots,
+              const void* t_dev, int time_dtype, int64_t B, int H, int C, int Tn, int method, int dtype) {
+  if (!out || !in || !series || !coef || !knots) return fail(XDE_EBADARG, who + ": null pointer");
   if (B < 1 || H < 1 || C < 1) return fail(XDE_EBADARG, who + ": bad sizes (need B, H, C >= 1)");
   if (Tn < 2) return fail(XDE_EBADARG, who + ": bad sizes (need Tn >= 2)");
   if (dtype != XDE_F32 && dtype != XDE_F64) return fail(XDE_EBADARG, who + ": bad dtype");
@@ -281,9 +302,9 @@ int cde_check(const std::string& who, const void* out, const void* in, const voi
   if (method == XDE_HISTORY_BEZIER)
     return fail(XDE_EBADARG, who + ": XDE_HISTORY_BEZIER is not a control path (its four-row window does not pass through the data); "
                                    "XDE_HISTORY_LINEAR and XDE_HISTORY_CUBIC are served");
-  if (method != XDE_HISTORY_LINEAR && method != XDE_HISTORY_CUBIC) return fail(XDE_EBADARG, who + ": unknown method");
+  if (method != XDE_HISTORY_LINEAR && method != XDE_HISTORY_CUBIC && method != kCdeNatural) return fail(XDE_EBADARG, who + ": unknown method");
   const uintptr_t em = dtype == XDE_F32 ? 3u : 7u, tm = time_dtype == XDE_F32 ? 3u : 7u;
-  const void* ps[4] = {out, in, series, knots};
+  const void* ps[5] = {out, in, series, coef, knots};
   for (const void* p : ps)
     if (reinterpret_cast<uintptr_t>(p) & em) return fail(XDE_EBADARG, who + ": operand not aligned to its element type");
   if (t_dev && (reinterpret_cast<uintptr_t>(t_dev) & tm)) return fail(XDE_EBADARG, who + ": t_dev not aligned to its element type");
@@ -338,64 +359,86 @@ xde_cde_plan_t cde_plan(bool backward, const void* big, int64_t B, int H, int C,
   return p;
 }
 
-void cde_args(CdeArgs* a, const xde_cde_plan_t& p, void* out, const void* in, const void* series, const void* knots, const void* t_dev,
-              double t_host, int time_dtype, int64_t B, int H, int C, int Tn, int method) {
+void cde_args(CdeArgs* a, const xde_cde_plan_t& p, void* out, const void* in, const void* series, const void* coef, const void* knots,
+              const void* t_dev, double t_host, int time_dtype, int64_t B, int H, int C, int Tn, int method) {
   memset(a, 0, sizeof(*a));
-  a->out = out, a->in = in, a->series = series, a->knots = knots, a->t_dev = t_dev, a->t_host = t_host;
+  a->out = out, a->in = in, a->series = series, a->coef = coef, a->knots = knots, a->t_dev = t_dev, a->t_host = t_host;
   a->B = B, a->H = H, a->C = C, a->Tn = Tn, a->method = method, a->time_f64 = time_dtype == XDE_F64;
   a->R = p.R;
   for (a->r_log = 0; (1 << a->r_log) < a->R; ++a->r_log) {}
   a->S = p.S, a->Hc = p.Hc, a->Gb = p.Gb, a->lds = p.lds, a->nt = p.nt;
 }
 
-}  // namespace
-
 // (a launch that groups batch rows keeps their dX rows in LDS: GRP implies LDSDX)
-#define CDE_DISPATCH(KERNEL, TY)                                                                          \
+#define CDE_DISPATCH_(KERNEL, TY, NAT)                                                                    \
   do {                                                                                                    \
     if (p.vec) {                                                                                          \
-      if (p.grouped) XDE_LAUNCH((KERNEL<TY, true, true, true>), g, blk, st, prof, a);                     \
-      else if (p.lds) XDE_LAUNCH((KERNEL<TY, true, true, false>), g, blk, st, prof, a);                   \
-      else XDE_LAUNCH((KERNEL<TY, true, false, false>), g, blk, st, prof, a);                             \
+      if (p.grouped) XDE_LAUNCH((KERNEL<TY, true, true, true, NAT>), g, blk, st, prof, a);                \
+      else if (p.lds) XDE_LAUNCH((KERNEL<TY, true, true, false, NAT>), g, blk, st, prof, a);              \
+      else XDE_LAUNCH((KERNEL<TY, true, false, false, NAT>), g, blk, st, prof, a);                        \
     } else {                                                                                              \
-      if (p.grouped) XDE_LAUNCH((KERNEL<TY, false, true, true>), g, blk, st, prof, a);                    \
-      else if (p.lds) XDE_LAUNCH((KERNEL<TY, false, true, false>), g, blk, st, prof, a);                  \
-      else XDE_LAUNCH((KERNEL<TY, false, false, false>), g, blk, st, prof, a);                            \
+      if (p.grouped) XDE_LAUNCH((KERNEL<TY, false, true, true, NAT>), g, blk, st, prof, a);               \
+      else if (p.lds) XDE_LAUNCH((KERNEL<TY, false, true, false, NAT>), g, blk, st, prof, a);             \
+      else XDE_LAUNCH((KERNEL<TY, false, false, false, NAT>), g, blk, st, prof, a);                       \
     }                                                                                                     \
   } while (0)
+#define CDE_DISPATCH(KERNEL, TY)                             \
+  do {                                                       \
+    if (method == kCdeNatural) CDE_DISPATCH_(KERNEL, TY, true); \
+    else CDE_DISPATCH_(KERNEL, TY, false);                   \
+  } while (0)
+
+// the one launcher of both directions and every control: `who` has passed cde_check
+int cde_launch(bool backward, void* out, const void* in, const void* series, const void* coef, const void* knots, const void* t_dev,
+               double t_host, int time_dtype, int64_t B, int H, int C, int Tn, int method, int dtype, void* stream) {
+  const xde_cde_plan_t p = cde_plan(backward, backward ? out : in, B, H, C, dtype);
+  CdeArgs a;
+  cde_args(&a, p, out, in, series, coef, knots, t_dev, t_host, time_dtype, B, H, C, Tn, method);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const double es = dtype == XDE_F32 ? 4.0 : 8.0;
+  const double rows = method == kCdeNatural ? 4.0 : 3.0;  // control rows read per batch row
+  ProfScope prof(XDE_KID_DENSE, (double(B) * H * C + double(B) * H + rows * double(B) * C) * es);
+  dim3 g(static_cast<unsigned>(p.blocks)), blk(kBlock);
+  if (!backward) {
+    if (dtype == XDE_F32) CDE_DISPATCH(xde_cde_contract_kernel, float);
+    else CDE_DISPATCH(xde_cde_contract_kernel, double);
+  } else {
+    if (dtype == XDE_F32) CDE_DISPATCH(xde_cde_backward_kernel, float);
+    else CDE_DISPATCH(xde_cde_backward_kernel, double);
+  }
+  HIP_TRY(hipGetLastError());
+  return XDE_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
 int xde_cde_contract(void* out, const void* F, const void* series, const void* knots, const void* t_dev, double t_host, int time_dtype,
                      int64_t B, int H, int C, int Tn, int method, int dtype, void* stream) {
-  if (int rc = cde_check("xde_cde_contract", out, F, series, knots, t_dev, time_dtype, B, H, C, Tn, method, dtype)) return rc;
-  const xde_cde_plan_t p = cde_plan(false, F, B, H, C, dtype);
-  CdeArgs a;
-  cde_args(&a, p, out, F, series, knots, t_dev, t_host, time_dtype, B, H, C, Tn, method);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const double es = dtype == XDE_F32 ? 4.0 : 8.0;
-  ProfScope prof(XDE_KID_DENSE, (double(B) * H * C + double(B) * H + 3.0 * double(B) * C) * es);
-  dim3 g(static_cast<unsigned>(p.blocks)), blk(kBlock);
-  if (dtype == XDE_F32) CDE_DISPATCH(xde_cde_contract_kernel, float);
-  else CDE_DISPATCH(xde_cde_contract_kernel, double);
-  HIP_TRY(hipGetLastError());
-  return XDE_OK;
+  if (method == kCdeNatural) return fail(XDE_EBADARG, "xde_cde_contract: unknown method");
+  if (int rc = cde_check("xde_cde_contract", out, F, series, series, knots, t_dev, time_dtype, B, H, C, Tn, method, dtype)) return rc;
+  return cde_launch(false, out, F, series, series, knots, t_dev, t_host, time_dtype, B, H, C, Tn, method, dtype, stream);
 }
 
 int xde_cde_contract_backward(void* gF, const void* gout, const void* series, const void* knots, const void* t_dev, double t_host,
                               int time_dtype, int64_t B, int H, int C, int Tn, int method, int dtype, void* stream) {
-  if (int rc = cde_check("xde_cde_contract_backward", gF, gout, series, knots, t_dev, time_dtype, B, H, C, Tn, method, dtype)) return rc;
-  const xde_cde_plan_t p = cde_plan(true, gF, B, H, C, dtype);
-  CdeArgs a;
-  cde_args(&a, p, gF, gout, series, knots, t_dev, t_host, time_dtype, B, H, C, Tn, method);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const double es = dtype == XDE_F32 ? 4.0 : 8.0;
-  ProfScope prof(XDE_KID_DENSE, (double(B) * H * C + double(B) * H + 3.0 * double(B) * C) * es);
-  dim3 g(static_cast<unsigned>(p.blocks)), blk(kBlock);
-  if (dtype == XDE_F32) CDE_DISPATCH(xde_cde_backward_kernel, float);
-  else CDE_DISPATCH(xde_cde_backward_kernel, double);
-  HIP_TRY(hipGetLastError());
-  return XDE_OK;
+  if (method == kCdeNatural) return fail(XDE_EBADARG, "xde_cde_contract_backward: unknown method");
+  if (int rc = cde_check("xde_cde_contract_backward", gF, gout, series, series, knots, t_dev, time_dtype, B, H, C, Tn, method, dtype)) return rc;
+  return cde_launch(true, gF, gout, series, series, knots, t_dev, t_host, time_dtype, B, H, C, Tn, method, dtype, stream);
+}
+
+int xde_cde_contract_natural(void* out, const void* F, const void* Y, const void* M, const void* knots, const void* t_dev, double t_host,
+                             int time_dtype, int64_t B, int H, int C, int Tn, int dtype, void* stream) {
+  if (int rc = cde_check("xde_cde_contract_natural", out, F, Y, M, knots, t_dev, time_dtype, B, H, C, Tn, kCdeNatural, dtype)) return rc;
+  return cde_launch(false, out, F, Y, M, knots, t_dev, t_host, time_dtype, B, H, C, Tn, kCdeNatural, dtype, stream);
+}
+
+int xde_cde_contract_natural_backward(void* gF, const void* gout, const void* Y, const void* M, const void* knots, const void* t_dev,
+                                      double t_host, int time_dtype, int64_t B, int H, int C, int Tn, int dtype, void* stream) {
+  if (int rc = cde_check("xde_cde_contract_natural_backward", gF, gout, Y, M, knots, t_dev, time_dtype, B, H, C, Tn, kCdeNatural, dtype))
+    return rc;
+  return cde_launch(true, gF, gout, Y, M, knots, t_dev, t_host, time_dtype, B, H, C, Tn, kCdeNatural, dtype, stream);
 }
 
 int xde_cde_plan(int backward, const void* big, int64_t B, int H, int C, int dtype, xde_cde_plan_t* plan) {

@@ -2,7 +2,8 @@
 // of each formula, shared by the history gathers (xde_history.hip, xde_dense.hip: value and derivative rows written out) and the CDE
 // contraction (xde_cde.hip: the derivative row kept on chip).  What depends on the query time alone — the interval index
 // i = clip(bucketize(tau) - 1, 0, T-1), the basis weights, the scales — is a small table entry a workgroup builds once; what depends on
-// the series is a handful of ops per element.  The scale conventions are the reference's `_make_series`, as written.
+// the series is a handful of ops per element.  The scale conventions are the reference's `_make_series`, as written.  The natural cubic
+// spline at the end is the project's own (include/xde_hip_spline.h): its gather (xde_spline.hip) and the CDE contraction share it.
 #pragma once
 
 #include "xde_common.hpp"
@@ -152,6 +153,52 @@ __device__ __forceinline__ void hermite_eval(const HermiteLag<T>& r, T X, T Y, T
   const T d0 = n0 / r.ha, d1 = n1 / r.hb;
   val = (((r.c0 * p0 + r.c1 * p1) + r.c2 * d0) + r.c3 * d1) * r.h1;
   der = ((r.g0 * p0 + r.g1 * p1) + r.g2 * d0) + r.g3 * d1;
+}
+
+// ------------------------------------------------------------------------------------------
+// NaturalCubicSpline (include/xde_hip_spline.h): the C2 cubic through Y with second derivatives M, both dense on the knot grid
+// ------------------------------------------------------------------------------------------
+template <typename T>
+struct NaturalLag {
+  int i, pad;          // i = clip(#{k : t_k <= tau} - 1, 0, Tn - 2): the rows are i and i + 1
+  T h, s, h6, s2, s6;  // h = t_{i+1} - t_i, s = tau - t_i, h / 6, s / 2, s / 6
+};
+
+// the table entry of a step s into an interval of length h (the coefficient build's fill calls this with the interval between two
+// observed nodes)
+template <typename T>
+__device__ __forceinline__ NaturalLag<T> make_natural_step(int i, T h, T s) {
+  NaturalLag<T> r;
+  r.i = i;
+  r.pad = 0;
+  r.h = h;
+  r.s = s;
+  r.h6 = h / T(6);
+  r.s2 = s / T(2);
+  r.s6 = s / T(6);
+  return r;
+}
+
+template <typename T>
+__device__ __forceinline__ NaturalLag<T> make_natural_lag(const T* __restrict__ ts, T tau, int Tn) {
+  int lo = 0, hi = Tn;
+  while (lo < hi) {
+    int mid = (lo + hi) >> 1;
+    if (ts[mid] <= tau) lo = mid + 1; else hi = mid;
+  }
+  int i = lo - 1;  // #{t_k <= tau} - 1: a query on a knot starts that knot's interval (s = 0, the value is Y_i exactly)
+  i = i < 0 ? 0 : (i > Tn - 2 ? Tn - 2 : i);
+  return make_natural_step<T>(i, ts[i + 1] - ts[i], tau - ts[i]);
+}
+
+// one element: Y0 = Y[i], Y1 = Y[i + 1], M0 = M[i], M1 = M[i + 1] of this column  ->  value and derivative
+template <typename T>
+__device__ __forceinline__ void natural_eval(const NaturalLag<T>& r, T Y0, T Y1, T M0, T M1, T& val, T& der) {
+  const T sl = (Y1 - Y0) / r.h;
+  const T d0 = sl - r.h6 * (T(2) * M0 + M1);
+  const T e = (M1 - M0) / r.h;
+  val = Y0 + r.s * (d0 + r.s * (M0 / T(2) + r.s6 * e));
+  der = d0 + r.s * (M0 + r.s2 * e);
 }
 
 }  // namespace xde

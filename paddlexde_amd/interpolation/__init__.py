@@ -7,12 +7,16 @@ launch: same constructor (``series [..., T, D]``, ``t [T]`` or None), same ``eva
 same conventions as written in the reference (``index = clip(bucketize(t) - 1, 0, T - 1)``, one-sided node derivatives for the cubic,
 row scales ``scale1..4``), in the package's default dtype float32 (interpolate_base.py:18,27-28) unless the series is float64.  Held to
 the reference's own tests for these classes (tests/interpolation/test_interpolation.py:13-85) in tests/_dde_cases.py.
+
+``NaturalCubicSpline`` is this project's own (the reference has none): the C2 natural cubic spline through the observed entries of a
+series on arbitrary strictly increasing knots, NaN meaning "not observed" — the control path of ``cdeint`` for irregularly sampled,
+partly observed data (include/xde_hip_spline.h states the path op for op).
 """
 import torch
 
 from .. import _hip
 
-__all__ = ["LinearInterpolation", "CubicHermiteSpline", "BezierSpline"]
+__all__ = ["LinearInterpolation", "CubicHermiteSpline", "BezierSpline", "NaturalCubicSpline"]
 
 
 class InterpolationBase:
@@ -83,3 +87,42 @@ class BezierSpline(InterpolationBase):
 
     method = "bez"
     min_times = 4
+
+
+class NaturalCubicSpline(InterpolationBase):
+    """The natural cubic spline through the observed entries of ``series [..., T, C]`` over strictly increasing ``t [T]`` (any spacing;
+    default the unit grid).  A NaN entry is "not observed": each column is interpolated through its own observed points; a NaN at
+    the first (last) time takes the column's first (last) observed value, so the path is C2 on the whole ``interval`` and its
+    derivative — what ``cdeint`` contracts with — is C1.  A column with no observed value is refused.
+
+    Construction runs one coefficient launch (xde_spline_natural_coeffs) after one host read that checks ``t`` and the columns;
+    ``evaluate`` / ``derivative`` are one xde_spline_natural_gather launch, and give the bits the CDE contraction builds on chip.
+    ``_series`` holds the values on the full knot grid (missing entries filled from the spline), ``_coef`` the second derivatives."""
+
+    method = "natural"
+    min_times = 2
+
+    def __init__(self, series, t=None, **kwargs):
+        super().__init__(series, t, **kwargs)
+        raw = self._series
+        columns = raw.reshape((-1,) + tuple(raw.shape[-2:]))
+        rising = (self._t[1:] > self._t[:-1]).all()  # (false for a NaN time too)
+        empty = torch.isnan(columns).all(dim=-2).any()
+        rising, empty = torch.stack([rising, empty]).tolist()  # the one host read
+        if not rising:
+            raise ValueError("NaturalCubicSpline: t must be strictly increasing")
+        if empty:
+            raise ValueError("NaturalCubicSpline: a column of the series has no observed (non-NaN) value: there is nothing to "
+                             "interpolate; drop the channel or fill it")
+        Y, M = torch.empty_like(columns), torch.empty_like(columns)
+        self._backend._spline_natural_coeffs(Y, M, columns, self._t)
+        self._series = Y.reshape(raw.shape)
+        self._coef = M.reshape(raw.shape)
+
+    def _gather(self, t):
+        tq = torch.as_tensor(t).detach().to(device=self._series.device, dtype=self._series.dtype).contiguous().reshape(-1)
+        shape = tuple(self._series.shape[:-2]) + (tq.numel(), self._series.shape[-1])
+        val = torch.empty(shape, dtype=self._series.dtype, device=self._series.device)
+        der = torch.empty_like(val)
+        self._backend._spline_natural_gather(val, der, self._series, self._coef, self._t, tq)
+        return val, der

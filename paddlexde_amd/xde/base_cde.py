@@ -8,16 +8,19 @@ back the outer product ``gF[b, h, c] = gout[b, h] * X'(t)[b, c]``): one launch e
 (include/xde_hip_cde.h), which build ``X'(t)`` on chip from the series with the device functions of the history gathers — the bits
 ``X.derivative(t)`` returns — and never write it out.
 
-The control path.  ``CubicHermiteSpline`` (one-sided node differences: the reference's, and the path neural-CDE users already use) has a
-continuous derivative and works with every solver.  ``LinearInterpolation`` has a derivative that jumps at every knot: fixed-step
-solvers with the knots on their grid integrate it, adaptive ones are refused.  ``BezierSpline`` is refused: its sliding four-row window
-is not a path through the data.  The spline classes keep the reference's scale conventions as written; these are exact on a uniform knot
-grid — the default ``t=None`` — so put time into the series as a channel for irregularly sampled data.
+The control path.  ``NaturalCubicSpline`` (this project's own: xde_cde_contract_natural / _backward, include/xde_hip_spline.h) is the
+C2 natural cubic spline through the observed entries of the series on arbitrary knots — NaN means "not observed" — so ``X'(t)`` is C1
+and every solver serves it: the control for irregularly sampled or partly observed data.  ``CubicHermiteSpline`` (one-sided node
+differences: the reference's) has a continuous derivative and works with every solver.  ``LinearInterpolation`` has a derivative that
+jumps at every knot: fixed-step solvers with the knots on their grid integrate it, adaptive ones are refused.  ``BezierSpline`` is
+refused: its sliding four-row window is not a path through the data.  ``CubicHermiteSpline`` and ``LinearInterpolation`` keep the
+reference's scale conventions as written; these are exact on a uniform knot grid — the default ``t=None`` — only: for irregularly
+sampled data use ``NaturalCubicSpline``.
 """
 import torch
 
 from .. import _hip
-from ..interpolation import BezierSpline, CubicHermiteSpline, InterpolationBase, LinearInterpolation
+from ..interpolation import BezierSpline, CubicHermiteSpline, InterpolationBase, LinearInterpolation, NaturalCubicSpline
 from .base_ode import BaseODE
 
 __all__ = ["BaseCDE", "CDEField", "CdeContractFn"]
@@ -26,27 +29,35 @@ __all__ = ["BaseCDE", "CDEField", "CdeContractFn"]
 class CdeContractFn(torch.autograd.Function):
     """``out[b, h] = sum_c F[b, h, c] * X'(t)[b, c]`` for contiguous ``F [B, H, C]``, ``series [B, Tn, C]``, ``knots [Tn]`` and ``t`` a
     one-element device tensor (read by the kernel: no synchronisation, so a captured call replays with the element's current value) or
-    a Python number.  Gradient to ``F`` only — the contraction is linear in it; the series, the knots and ``t`` get none."""
+    a Python number.  With ``method`` "natural", ``series`` is the spline's ``Y`` and ``coef [B, Tn, C]`` its second derivatives ``M``.
+    Gradient to ``F`` only — the contraction is linear in it; the series, the coefficients, the knots and ``t`` get none."""
 
     @staticmethod
-    def forward(ctx, F, series, knots, t, method):
+    def forward(ctx, F, series, knots, t, method, coef=None):
         be = _hip.get_backend()
         F = F.contiguous()
         out = torch.empty(F.shape[:2], dtype=F.dtype, device=F.device)  # (torch's allocator: capture-safe)
-        be._cde_contract(out, F, series, knots, t, method)
+        if method == "natural":
+            be._cde_contract_natural(out, F, series, coef, knots, t)
+        else:
+            be._cde_contract(out, F, series, knots, t, method)
         ctx.method, ctx.t_host = method, None if torch.is_tensor(t) else t
-        ctx.save_for_backward(series, knots, *([t] if torch.is_tensor(t) else []))
+        ctx.save_for_backward(series, knots, *([coef] if method == "natural" else []), *([t] if torch.is_tensor(t) else []))
         ctx.f_shape = F.shape
         return out
 
     @staticmethod
     def backward(ctx, gout):
         series, knots, *rest = ctx.saved_tensors
+        coef = rest.pop(0) if ctx.method == "natural" else None
         t = rest[0] if rest else ctx.t_host
         gout = gout.contiguous()
         gF = torch.empty(ctx.f_shape, dtype=gout.dtype, device=gout.device)
-        _hip.get_backend()._cde_contract_backward(gF, gout, series, knots, t, ctx.method)
-        return gF, None, None, None, None
+        if coef is not None:
+            _hip.get_backend()._cde_contract_natural_backward(gF, gout, series, coef, knots, t)
+        else:
+            _hip.get_backend()._cde_contract_backward(gF, gout, series, knots, t, ctx.method)
+        return gF, None, None, None, None, None
 
 
 def _kernel_time(t, series):
@@ -67,16 +78,17 @@ class CDEField(torch.nn.Module):
     """The vector field ``(t, z) -> func(t, z) . X'(t)`` of the CDE ``dz = func(t, z) dX(t)``.
 
     ``func(t, z)`` returns ``[..., H, C]`` for ``z`` of shape ``[..., H]``, in ``z``'s dtype on ``z``'s device; ``X`` is a
-    ``CubicHermiteSpline`` or ``LinearInterpolation`` over a series ``[..., T, C]`` with the same leading dimensions (flattened to one
+    ``NaturalCubicSpline``, ``CubicHermiteSpline`` or ``LinearInterpolation`` over a series ``[..., T, C]`` with the same leading dimensions (flattened to one
     batch dimension for the kernel).  ``func`` is a submodule when it is a module, so its parameters are this module's."""
 
     def __init__(self, func, X):
         super().__init__()
         if isinstance(X, BezierSpline):
             raise NotImplementedError("a BezierSpline is not a control path: its sliding four-row window does not pass through the "
-                                      "data; use CubicHermiteSpline (or LinearInterpolation with a fixed-step solver)")
-        if not isinstance(X, (LinearInterpolation, CubicHermiteSpline)):
-            raise TypeError("X must be a paddlexde_amd.interpolation CubicHermiteSpline or LinearInterpolation, got {}".format(
+                                      "data; use CubicHermiteSpline (or LinearInterpolation with a fixed-step solver), or NaturalCubicSpline for "
+                                      "irregularly sampled or partly observed data")
+        if not isinstance(X, (LinearInterpolation, CubicHermiteSpline, NaturalCubicSpline)):
+            raise TypeError("X must be a paddlexde_amd.interpolation CubicHermiteSpline or LinearInterpolation, or NaturalCubicSpline, got {}".format(
                 type(X).__name__ if isinstance(X, InterpolationBase) else type(X)))
         self.func = func
         d = self.__dict__
@@ -86,6 +98,7 @@ class CDEField(torch.nn.Module):
         d["_series"] = series.reshape((-1,) + tuple(series.shape[-2:]))
         d["_knots"] = X._t
         d["_method"] = X.method
+        d["_coef"] = X._coef.reshape(d["_series"].shape) if isinstance(X, NaturalCubicSpline) else None
 
     def forward(self, t, z):
         F = self.func(t, z)
@@ -103,7 +116,7 @@ class CDEField(torch.nn.Module):
             raise ValueError("z has leading dimensions {} and the control's series {}: they must be the same".format(
                 tuple(z.shape[:-1]), self._lead))
         H = z.shape[-1]
-        out = CdeContractFn.apply(F.reshape(-1, H, C), series, self._knots, _kernel_time(t, series), self._method)
+        out = CdeContractFn.apply(F.reshape(-1, H, C), series, self._knots, _kernel_time(t, series), self._method, self._coef)
         return out.reshape(z.shape)
 
 
@@ -115,15 +128,17 @@ def check_cde_problem(X, z0, t_span, solver):
         raise NotImplementedError("cdeint takes a tensor z0, not a tuple: stack the members into one state tensor [..., H]")
     if isinstance(X, BezierSpline):
         raise NotImplementedError("a BezierSpline is not a control path: its sliding four-row window does not pass through the "
-                                  "data; use CubicHermiteSpline (or LinearInterpolation with a fixed-step solver)")
-    if not isinstance(X, (LinearInterpolation, CubicHermiteSpline)):
-        raise TypeError("X must be a paddlexde_amd.interpolation CubicHermiteSpline or LinearInterpolation, got {}".format(type(X)))
+                                  "data; use CubicHermiteSpline (or LinearInterpolation with a fixed-step solver), or NaturalCubicSpline for "
+                                      "irregularly sampled or partly observed data")
+    if not isinstance(X, (LinearInterpolation, CubicHermiteSpline, NaturalCubicSpline)):
+        raise TypeError("X must be a paddlexde_amd.interpolation CubicHermiteSpline or LinearInterpolation, or NaturalCubicSpline, got {}".format(
+            type(X)))
     fixed = isinstance(solver, type) and issubclass(solver, FixedSolver)
     if isinstance(X, LinearInterpolation) and not fixed:
         raise NotImplementedError("LinearInterpolation with an adaptive solver: the control's derivative jumps at every knot and the "
                                   "adaptive solvers do not take jump times (jump_t), so the step size underflows at tight tolerances; "
                                   "use CubicHermiteSpline, whose derivative is continuous, or a fixed-step solver with the knots on "
-                                  "its grid")
+                                  "its grid (or NaturalCubicSpline, which is C2)")
     if not torch.is_tensor(t_span):
         t_span = torch.as_tensor(t_span)
     if torch.is_grad_enabled() and t_span.requires_grad:
