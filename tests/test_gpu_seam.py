@@ -10,14 +10,18 @@ the same sums by construction (one workgroup's worth of vectors: every other ter
 
 Shapes (fp32 lanes hold 4 elements, fp64 lanes 2): 1 and 7 elements — scalar tail only; 1027 — vector body + tail, fewer lanes than one
 workgroup (fp32); 256*4*3 + 5 — several workgroups, uneven; 1 200 003 — every lane of the 512-workgroup grid carries 3 (fp32) or 5 (fp64)
-vectors per array."""
+vectors per array.
+
+test_solver_variants: what else a solve hands to the launch — NORM_LINF, Bosh3's pair (a21 = 1/2, another last error coefficient, order
+3), reverse time, `step_t`, `max_step` / `min_step`, the PI controller — on 1027 and 3077 elements, against the three launches as above;
+a state that leaves the finite range ends in the three launches' exception.  tests/test_gpu_seam_kernel.py calls the launch directly."""
 import numpy as np
 import pytest
 import torch
 
 from oracle import xde_oracle as O
-from paddlexde_amd import Dopri5, _hip
-from paddlexde_amd.utils import _rms_norm
+from paddlexde_amd import Bosh3, Dopri5, _hip
+from paddlexde_amd.utils import _linf_norm, _rms_norm
 from paddlexde_amd.xde import BaseODE
 
 from . import problems as P
@@ -32,6 +36,10 @@ class Dopri5ThreeLaunches(Dopri5):
     SINGLE_MAX_ELEMS = 0  # no one-workgroup error-norm + controller kernel: the three launches the seam replaces, at every size
 
 
+class Bosh3ThreeLaunches(Bosh3):
+    SINGLE_MAX_ELEMS = 0
+
+
 @pytest.fixture
 def dev():
     return torch.device("cuda")
@@ -41,11 +49,11 @@ def _block(c):
     return tuple(getattr(c, f) for f in FIELDS) + tuple(c.ratio_seg)
 
 
-def _solve(dev, cls, seam, pipeline, dtype, shape, t_end=12.0, count=None, **kw):
+def _solve(dev, cls, seam, pipeline, dtype, shape, t_end=12.0, count=None, norm=_rms_norm, t_start=0.0, **kw):
     prob = P.Linear(dim=shape[1], seed=3)
     y0 = torch.randn(*shape, generator=torch.Generator().manual_seed(1)).to(dtype).to(dev)
-    t = torch.linspace(0.0, t_end, 5, dtype=dtype)
-    s = cls(xde=BaseODE(prob.f_torch(dev), y0=y0, t_span=t), y0=y0, rtol=1e-6, atol=1e-8, norm=_rms_norm, dtype=dtype, pipeline=pipeline,
+    t = torch.linspace(t_start, t_end, 5, dtype=dtype)
+    s = cls(xde=BaseODE(prob.f_torch(dev), y0=y0, t_span=t), y0=y0, rtol=1e-6, atol=1e-8, norm=norm, dtype=dtype, pipeline=pipeline,
             record_trace=True, seam=seam, **kw)
     be = s.backend
     if count is not None:
@@ -84,6 +92,69 @@ def test_accept_path_with_interior_output_times(dev, shape, dtype, pipeline):
     vectors = numel // (4 if dtype == torch.float32 else 2)
     if vectors <= 256 or numel > Dopri5.SINGLE_MAX_ELEMS:  # the default path's sums are these sums (module docstring)
         _same(got, _solve(dev, Dopri5, "launches", pipeline, dtype, SHAPES[shape]))
+
+
+# what the host hands to the seam launch beyond the default solve: (solver, options of _solve)
+VARIANTS = {
+    "linf": (Dopri5ThreeLaunches, dict(norm=_linf_norm, first_step=0.5)),
+    "bosh3_rms": (Bosh3ThreeLaunches, dict(t_end=2.0)),  # a21 = 1/2, another c_last, order 3
+    "bosh3_linf": (Bosh3ThreeLaunches, dict(t_end=2.0, norm=_linf_norm)),
+    "reverse_time": (Dopri5ThreeLaunches, dict(t_start=12.0, t_end=0.0)),
+    "step_t": (Dopri5ThreeLaunches, dict(step_t=[1.7, 5.1])),
+    "max_step": (Dopri5ThreeLaunches, dict(max_step=0.3)),
+    "min_step": (Dopri5ThreeLaunches, dict(min_step=0.2)),
+    "pi_rms": (Dopri5ThreeLaunches, dict(controller="PI")),
+    "pi_linf": (Dopri5ThreeLaunches, dict(controller="PI", norm=_linf_norm)),
+}
+
+
+@pytest.mark.parametrize("pipeline", ["sync", "lag"])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64], ids=["f32", "f64"])
+@pytest.mark.parametrize("shape", ["n1027", "n3077"])
+@pytest.mark.parametrize("variant", list(VARIANTS))
+def test_solver_variants(dev, variant, shape, dtype, pipeline):
+    """The other instantiations and operands a solve hands over — NORM_LINF, Bosh3's pair, reverse time, `step_t`, the step clamps, the
+    PI controller: rows, trace, mirror, device block and stats of the three launches, and the seam did run."""
+    cls, kw = VARIANTS[variant]
+    n = []
+    got = _solve(dev, cls, "resident", pipeline, dtype, SHAPES[shape], count=n, **kw)
+    want = _solve(dev, cls, "launches", pipeline, dtype, SHAPES[shape], **kw)
+    assert len(n) >= 3, len(n)
+    _same(got, want)
+
+
+class _Square(torch.nn.Module):
+    def forward(self, t, y):
+        return y * y
+
+
+@pytest.mark.parametrize("pipeline", ["sync", "lag"])
+def test_a_state_that_leaves_the_finite_range_ends_as_under_the_launches(dev, pipeline):
+    """y' = y^2 from 1 has its pole at t = 1: the solve to t = 2 ends in the exception (type and message, the step included) it ends in
+    under the three launches, after seam launches, and nothing names the grid barrier."""
+    def run(seam, count=None):
+        y0 = torch.ones(*SHAPES["n1027"], dtype=torch.float64, device=dev)
+        t = torch.tensor([0.0, 2.0], dtype=torch.float64)
+        s = Dopri5ThreeLaunches(xde=BaseODE(_Square(), y0=y0, t_span=t), y0=y0, rtol=1e-6, atol=1e-8, norm=_rms_norm, dtype=torch.float64,
+                                pipeline=pipeline, seam=seam)
+        be = s.backend
+        if count is not None:
+            real = be._seam_attempt
+            be._seam_attempt = lambda *a, **k: (count.append(1), real(*a, **k))[1]
+        try:
+            with pytest.raises(Exception) as e:
+                s.integrate(t)
+            torch.cuda.synchronize()
+            assert be._seam_expired(s._ctrl) == 0
+        finally:
+            if count is not None:
+                del be._seam_attempt
+        return type(e.value), str(e.value)
+
+    n = []
+    got, want = run("resident", n), run("launches")
+    assert got == want and len(n) >= 3, (got, want, len(n))
+    assert got[0] is AssertionError and "grid barrier" not in got[1] and ("underflow" in got[1] or "non-finite" in got[1]), got
 
 
 def _advance(dev, seam, pipeline, dtype, shape, budgets, **kw):
