@@ -11,7 +11,11 @@ knots (gradients through the steps), or with ``--adjoint`` through ``cdeint_adjo
 the series' own times.  With it ``--irregular`` samples the spirals at times drawn from the seed (not ``linspace``) and ``--missing P``
 sets a share ``P`` of the x / y entries to NaN ("not observed"), also from the seed.
 
-    python examples/cde_demo.py --max-steps 60 [--adjoint] [--control natural [--irregular] [--missing 0.3]]
+``--encoder`` puts a small trainable map in front of the spline — a per-channel affine on x and y (time, the knots' channel, passes
+through; unobserved entries stay unobserved) — and trains it through the control: the spline is rebuilt from the encoded series each
+iteration with ``differentiable=True``, and ``cdeint`` / ``cdeint_adjoint`` carry the loss gradient back to the series.
+
+    python examples/cde_demo.py --max-steps 60 [--adjoint] [--control natural [--irregular] [--missing 0.3]] [--encoder]
 """
 import argparse
 import math
@@ -67,16 +71,36 @@ class CDEFunc(nn.Module):
         return self.net(z).reshape(z.shape + (CHANNELS,))
 
 
+class ChannelAffine(nn.Module):
+    """series [B, T, C] -> the same with x and y scaled and shifted per channel (starts as the identity).  Time passes through; a NaN
+    entry stays NaN and takes no part in the gradient."""
+
+    def __init__(self):
+        super().__init__()
+        self.scale = nn.Parameter(torch.ones(CHANNELS - 1))
+        self.shift = nn.Parameter(torch.zeros(CHANNELS - 1))
+
+    def forward(self, series):
+        seen = ~torch.isnan(series)
+        filled = torch.nan_to_num(series, nan=0.0)
+        mapped = torch.cat([filled[..., :1], filled[..., 1:] * self.scale + self.shift], dim=-1)
+        return torch.where(seen, mapped, series)
+
+
 class NeuralCDE(nn.Module):
-    def __init__(self, hidden=8):
+    def __init__(self, hidden=8, encoder=False):
         super().__init__()
         self.initial = nn.Linear(CHANNELS, hidden)
         self.func = CDEFunc(hidden)
         self.readout = nn.Linear(hidden, 1)
+        if encoder:
+            self.encoder = ChannelAffine()
 
-    def forward(self, X, adjoint=False):
+    def forward(self, X, adjoint=False, first=None):
+        """``first``: the control's value at the first knot where ``X.evaluate`` is not differentiable (a differentiable cubic
+        Hermite control: it is the series' first row)."""
         knots = X.grid_points
-        z0 = self.initial(X.evaluate(knots[:1])[:, 0, :])  # [B, H]
+        z0 = self.initial(X.evaluate(knots[:1])[:, 0, :] if first is None else first)  # [B, H]
         if adjoint:
             zT = cdeint_adjoint(self.func, X, z0, knots[[0, -1]], solver=Dopri5, rtol=1e-3, atol=1e-5)[-1]
         else:
@@ -85,7 +109,7 @@ class NeuralCDE(nn.Module):
 
 
 def train(max_steps=60, n=128, length=32, hidden=8, seed=0, device="cuda:0", adjoint=False, log_every=10, control="cubic", irregular=False,
-          missing=0.0):
+          missing=0.0, encoder=False):
     if control not in ("cubic", "natural"):
         raise ValueError("control must be 'cubic' or 'natural', got {!r}".format(control))
     if control == "cubic" and (irregular or missing > 0.0):
@@ -93,13 +117,20 @@ def train(max_steps=60, n=128, length=32, hidden=8, seed=0, device="cuda:0", adj
                          "uniform-grid conventions and has no notion of an unobserved entry")
     torch.manual_seed(seed)
     series, labels = make_data(n, length, seed, device, irregular, missing)
-    X = CubicHermiteSpline(series) if control == "cubic" else NaturalCubicSpline(series, series[0, :, 0])  # (channel 0 is the time)
-    model = NeuralCDE(hidden).to(device)
+    make = (lambda x, **kw: CubicHermiteSpline(x, **kw)) if control == "cubic" else (
+        lambda x, **kw: NaturalCubicSpline(x, series[0, :, 0], **kw))  # (channel 0 is the time)
+    X = None if encoder else make(series)
+    model = (NeuralCDE(hidden, encoder=True) if encoder else NeuralCDE(hidden)).to(device)
     opt = torch.optim.Adam(model.parameters(), lr=1e-2)
     losses = []
     t0 = time.perf_counter()
     for step in range(1, max_steps + 1):
-        logits = model(X, adjoint)
+        if encoder:
+            # the control comes from something that is trained: rebuilt each iteration, attached to the encoder's graph
+            encoded = model.encoder(series)
+            logits = model(make(encoded, differentiable=True), adjoint, first=encoded[:, 0, :] if control == "cubic" else None)
+        else:
+            logits = model(X, adjoint)
         loss = nn.functional.binary_cross_entropy_with_logits(logits, labels)
         opt.zero_grad()
         loss.backward()
@@ -119,6 +150,7 @@ if __name__ == "__main__":
     ap.add_argument("--control", choices=("cubic", "natural"), default="cubic", help="the control path through the series")
     ap.add_argument("--irregular", action="store_true", help="sample times drawn from the seed (needs --control natural)")
     ap.add_argument("--missing", type=float, default=0.0, metavar="P", help="share of x / y entries set to NaN (needs --control natural)")
+    ap.add_argument("--encoder", action="store_true", help="train a per-channel affine in front of the spline through differentiable=True")
     a = ap.parse_args()
-    ls = train(a.max_steps, adjoint=a.adjoint, control=a.control, irregular=a.irregular, missing=a.missing)
+    ls = train(a.max_steps, adjoint=a.adjoint, control=a.control, irregular=a.irregular, missing=a.missing, encoder=a.encoder)
     print("first loss {:.4f} -> last loss {:.4f}".format(ls[0], ls[-1]))

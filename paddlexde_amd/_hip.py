@@ -238,6 +238,22 @@ SPLINE_PROTOTYPES = {
     "xde_cde_contract_natural": (_i32, [_vp] * 6 + [_dbl, _i32, _i64, _i32, _i32, _i32, _i32, _vp]),
     "xde_cde_contract_natural_backward": (_i32, [_vp] * 6 + [_dbl, _i32, _i64, _i32, _i32, _i32, _i32, _vp]),
 }
+class XdeCdeGradPlan(C.Structure):
+    """Mirror of xde_cdegrad_plan_t (include/xde_hip_cdegrad.h)."""
+
+    _fields_ = [(name, C.c_int32) for name in ("vec", "P", "CL", "chunks", "rows", "strided")] + [("blocks", C.c_int64)]
+
+
+# the entry points of include/xde_hip_cdegrad.h (the gradient of cdeint with respect to its control path: the control's cotangent in the
+# contraction, the transposes of the natural spline's coefficient build and gather); bound by load_library() after _bind_spline
+CDEGRAD_PROTOTYPES = {
+    "xde_cde_control_grad": (_i32, [_vp] * 5 + [_dbl, _i32, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "xde_cde_control_grad_natural": (_i32, [_vp] * 6 + [_dbl, _i32, _i64, _i32, _i32, _i32, _i32, _vp]),
+    "xde_cde_control_grad_plan": (_i32, [_vp, _i64, _i32, _i32, _i32, C.POINTER(XdeCdeGradPlan)]),
+    "xde_spline_natural_coeffs_backward": (_i32, [_vp] * 6 + [_i64, _i32, _i32, _i32, _vp]),
+    "xde_spline_natural_coeffs_backward_workspace_bytes": (_i64, [_i64, _i32, _i32, _i32]),
+    "xde_spline_natural_gather_backward": (_i32, [_vp] * 6 + [_i64, _i32, _i32, _i32, _i32, _vp]),
+}
 SYMBOLS = tuple(PROTOTYPES)
 BACKPROP_SYMBOLS = tuple(BACKPROP_PROTOTYPES)
 GRID_SYMBOLS = tuple(GRID_PROTOTYPES)
@@ -245,6 +261,7 @@ SDE_SYMBOLS = tuple(SDE_PROTOTYPES)
 CDE_SYMBOLS = tuple(CDE_PROTOTYPES)
 SEAM_SYMBOLS = tuple(SEAM_PROTOTYPES)
 SPLINE_SYMBOLS = tuple(SPLINE_PROTOTYPES)
+CDEGRAD_SYMBOLS = tuple(CDEGRAD_PROTOTYPES)
 XDE_INTERP_MAX_ROWS = 8
 XDE_INTERP_LINEAR, XDE_INTERP_CUBIC = 0, 1
 XDE_ROW_INTERP, XDE_ROW_COPY_A, XDE_ROW_COPY_B = 0, 1, 2
@@ -276,7 +293,7 @@ _REBUILD = "rebuild it with `python -m paddlexde_amd.csrc.build --force`"
 
 
 def _declare(lib, sym):
-    proto = PROTOTYPES.get(sym) or BACKPROP_PROTOTYPES.get(sym) or GRID_PROTOTYPES.get(sym) or SDE_PROTOTYPES.get(sym) or CDE_PROTOTYPES.get(sym) or SEAM_PROTOTYPES.get(sym) or SPLINE_PROTOTYPES[sym]
+    proto = PROTOTYPES.get(sym) or BACKPROP_PROTOTYPES.get(sym) or GRID_PROTOTYPES.get(sym) or SDE_PROTOTYPES.get(sym) or CDE_PROTOTYPES.get(sym) or SEAM_PROTOTYPES.get(sym) or SPLINE_PROTOTYPES.get(sym) or CDEGRAD_PROTOTYPES[sym]
     try:
         fn = getattr(lib, sym)
     except AttributeError:
@@ -334,6 +351,12 @@ def _bind_spline(lib):
         _declare(lib, sym)
 
 
+def _bind_cdegrad(lib):
+    """Declare the entry points of include/xde_hip_cdegrad.h on ``lib`` (after ``_bind``: the ABI check comes first)."""
+    for sym in CDEGRAD_SYMBOLS:
+        _declare(lib, sym)
+
+
 def load_library():
     """dlopen libxde_hip.so and declare prototypes.  Raises if it has not been built, or is not the library this binding speaks to."""
     global _lib
@@ -354,6 +377,7 @@ def load_library():
         _bind_cde(lib)
         _bind_seam(lib)
         _bind_spline(lib)
+        _bind_cdegrad(lib)
         _lib = lib
     return _lib
 
@@ -1122,6 +1146,88 @@ class HipBackend:
     def _cde_contract_natural_backward(self, gF, gout, Y, M, knots, t):
         """``gF[b, h, c] = gout[b, h] * dX[b, c]``: the cotangent of ``_cde_contract_natural``'s F.  One launch."""
         self._cde_natural_call("_cde_contract_natural_backward", gF, gout, Y, M, knots, t)
+
+    # -- the gradient with respect to the control path (include/xde_hip_cdegrad.h) -----------------------------------------------------
+    # Private for the reason the _cde_* methods are.  CdeControlContractFn (xde/base_cde.py) and the differentiable splines
+    # (interpolation) call these.
+    def _cde_grad_operands(self, who, outs, gout, F, knots, t, Tn):
+        self._spline_operands(who, *outs, gout, F, knots)
+        if F.dim() != 3 or gout.dim() != 2 or tuple(gout.shape) != tuple(F.shape[:2]) or tuple(knots.shape) != (Tn,):
+            raise XdeError("{}: expected gout [B, H], F [B, H, C] and knots [Tn], got {}, {}, {}".format(
+                who, tuple(gout.shape), tuple(F.shape), tuple(knots.shape)))
+        B, H, C_ = F.shape
+        for o in outs:
+            if tuple(o.shape) != (B, Tn, C_):
+                raise XdeError("{}: the control's cotangent must be [B, Tn, C] = {}, got {}".format(who, (B, Tn, C_), tuple(o.shape)))
+        if torch.is_tensor(t):
+            self._require_device(t)
+            if t.numel() != 1 or t.dtype not in (torch.float32, torch.float64) or t.device != F.device:
+                raise XdeError("{}: t must be ONE float32 / float64 element on the series' device (got shape {}, {}, {})".format(
+                    who, tuple(t.shape), t.dtype, t.device))
+            return B, H, C_, t.data_ptr(), 0.0, dtype_code(t.dtype)
+        return B, H, C_, None, float(t), XDE_F64
+
+    def _cde_control_grad(self, gSeries, gout, F, knots, t, method):
+        """``gSeries[b, k, c]``: the cotangent of the ``method`` ("linear" | "cubic") control's series in ``_cde_contract``, from ``gout
+        [B, H]`` and ``F [B, H, C]`` — ``gdX = sum_h gout * F`` scattered to the rows ``X'(t)`` read, ``+0`` elsewhere.  One launch that
+        writes every element of ``gSeries`` once."""
+        who = "_cde_control_grad"
+        B, H, C_, t_dev, t_host, tt = self._cde_grad_operands(who, (gSeries,), gout, F, knots, t, gSeries.shape[1] if gSeries.dim() == 3 else -1)
+        rc = self.lib.xde_cde_control_grad(gSeries.data_ptr(), gout.data_ptr(), F.data_ptr(), knots.data_ptr(), t_dev, t_host, tt, B, H, C_,
+                                           gSeries.shape[1], HISTORY_METHODS[method], dtype_code(F.dtype), self._stream(F))
+        self._check(rc, "xde_cde_control_grad")
+
+    def _cde_control_grad_natural(self, gY, gM, gout, F, knots, t):
+        """``gY, gM [B, Tn, C]``: the cotangents of the natural control's ``Y`` and ``M`` in ``_cde_contract_natural``.  One launch."""
+        who = "_cde_control_grad_natural"
+        B, H, C_, t_dev, t_host, tt = self._cde_grad_operands(who, (gY, gM), gout, F, knots, t, gY.shape[1] if gY.dim() == 3 else -1)
+        rc = self.lib.xde_cde_control_grad_natural(gY.data_ptr(), gM.data_ptr(), gout.data_ptr(), F.data_ptr(), knots.data_ptr(), t_dev,
+                                                   t_host, tt, B, H, C_, gY.shape[1], dtype_code(F.dtype), self._stream(F))
+        self._check(rc, "xde_cde_control_grad_natural")
+
+    def _cde_control_grad_plan(self, F, B, H, channels):
+        """The launch plan of ``_cde_control_grad`` / ``_natural`` for ``[B, H, channels]``, ``F``'s dtype and its alignment, as a dict
+        of xde_cdegrad_plan_t's fields.  Nothing is enqueued."""
+        plan = XdeCdeGradPlan()
+        rc = self.lib.xde_cde_control_grad_plan(F.data_ptr(), int(B), int(H), int(channels), dtype_code(F.dtype), C.byref(plan))
+        self._check(rc, "xde_cde_control_grad_plan")
+        return {name: int(getattr(plan, name)) for name, _ in XdeCdeGradPlan._fields_}
+
+    def _spline_natural_coeffs_backward(self, gSeries, gY, gM, series, knots):
+        """``gSeries [B, Tn, C]`` from the cotangents ``gY, gM`` of ``_spline_natural_coeffs``'s outputs: its transpose.  ``series`` is
+        read for its NaN pattern; an unobserved entry gets ``+0``.  One launch (its workspace comes from torch's allocator)."""
+        who = "_spline_natural_coeffs_backward"
+        self._spline_operands(who, gSeries, gY, gM, series, knots)
+        if series.dim() != 3 or not (gSeries.shape == gY.shape == gM.shape == series.shape) or tuple(knots.shape) != (series.shape[1],):
+            raise XdeError("{}: expected gSeries, gY, gM, series [B, Tn, C] and knots [Tn], got {}, {}, {}, {}, {}".format(
+                who, tuple(gSeries.shape), tuple(gY.shape), tuple(gM.shape), tuple(series.shape), tuple(knots.shape)))
+        B, Tn, C_ = series.shape
+        need = self.lib.xde_spline_natural_coeffs_backward_workspace_bytes(B, Tn, C_, dtype_code(series.dtype))
+        ws = torch.empty(need // series.element_size(), dtype=series.dtype, device=series.device)
+        rc = self.lib.xde_spline_natural_coeffs_backward(gSeries.data_ptr(), gY.data_ptr(), gM.data_ptr(), series.data_ptr(),
+                                                         knots.data_ptr(), ws.data_ptr(), B, Tn, C_, dtype_code(series.dtype),
+                                                         self._stream(series))
+        self._check(rc, "xde_spline_natural_coeffs_backward")
+
+    def _spline_natural_gather_backward(self, gY, gM, gval, gder, knots, tq):
+        """``gY, gM [..., Tn, D]`` from the cotangents ``gval`` and / or ``gder [..., L, D]`` (either may be None) of
+        ``_spline_natural_gather`` at ``tq [L]``: its transpose.  One launch, one owner per column."""
+        who = "_spline_natural_gather_backward"
+        self._spline_operands(who, *[x for x in (gY, gM, gval, gder, knots, tq) if x is not None])
+        g = gval if gval is not None else gder
+        if g is None:
+            raise XdeError("{}: needs gval or gder".format(who))
+        Tn, D = gY.shape[-2], gY.shape[-1]
+        if gM.shape != gY.shape or tuple(knots.shape) != (Tn,) or tuple(g.shape) != tuple(gY.shape[:-2]) + (tq.numel(), D) or (
+                gval is not None and gder is not None and gval.shape != gder.shape):
+            raise XdeError("{}: shapes do not agree: gY {}, gM {}, knots {}, tq {}, cotangent {}".format(
+                who, tuple(gY.shape), tuple(gM.shape), tuple(knots.shape), tuple(tq.shape), tuple(g.shape)))
+        if gY.numel() == 0:
+            return
+        rc = self.lib.xde_spline_natural_gather_backward(gY.data_ptr(), gM.data_ptr(), _ptr(gval), _ptr(gder), knots.data_ptr(),
+                                                         tq.data_ptr(), gY.numel() // (Tn * D), Tn, tq.numel(), D, dtype_code(gY.dtype),
+                                                         self._stream(gY))
+        self._check(rc, "xde_spline_natural_gather_backward")
 
     def hermite_gather(self, val, der, his, his_t, lags):
         """his [..., T, D] (contiguous), his_t [T], lags [L]  ->  val, der [..., L, D]."""

@@ -415,6 +415,10 @@ class AdjointProblem:
 
         if not callable(vjp):
             raise TypeError("AdjointProblem needs vjp(t, y, cotangent) -> (f, vjp_t, vjp_y, *vjp_params)")
+        if callable(getattr(func, "control_tensors", None)) and func.control_tensors():
+            raise NotImplementedError("a differentiable control with adjoint_options['vjp'] / AdjointProblem: the caller's "
+                                      "vector-Jacobian product does not return the control's cotangent; use cdeint_adjoint (torch "
+                                      "autograd takes the vjp), or build the control with differentiable=False")
         options = dict(options or {})
         importer = options.pop("from_dlpack", None) if from_dlpack is None else from_dlpack
         options.pop("from_dlpack", None)

@@ -23,12 +23,15 @@ class InterpolationBase:
     method = None  # "linear" | "cubic" | "bez": the kernels' name of the spline
     min_times = 2
 
-    def __init__(self, series, t=None, **kwargs):
+    def __init__(self, series, t=None, differentiable=False, **kwargs):
         be = _hip.get_backend()
         series = torch.as_tensor(series)
         be.require_device(series)
         dtype = series.dtype if series.dtype == torch.float64 else torch.float32  # (`default_type`: float32)
-        self._series = series.detach().to(dtype).contiguous()
+        # differentiable: the spline stays attached to the series' autograd graph, so that a control path of cdeint can come from
+        # something that is trained (xde/base_cde.py CdeControlContractFn); the knots never get a gradient
+        self.differentiable = bool(differentiable)
+        self._series = (series if self.differentiable else series.detach()).to(dtype).contiguous()
         n_times = self._series.shape[-2]
         if n_times < self.min_times:
             raise ValueError("{} needs at least {} time points".format(type(self).__name__, self.min_times))
@@ -52,6 +55,11 @@ class InterpolationBase:
         return torch.stack([self._t[0], self._t[-1]])
 
     def _gather(self, t):
+        if self.differentiable:
+            raise NotImplementedError(
+                "{}(differentiable=True): evaluate / derivative are not differentiable; the values at the knots are the series rows "
+                "themselves (index the series, e.g. series[..., 0, :] for z0), and cdeint differentiates X'(t) inside its "
+                "contraction; NaturalCubicSpline(differentiable=True) has differentiable evaluate / derivative".format(type(self).__name__))
         tq = torch.as_tensor(t).detach().to(device=self._series.device, dtype=self._series.dtype).contiguous().reshape(-1)
         shape = tuple(self._series.shape[:-2]) + (tq.numel(), self._series.shape[-1])
         val = torch.empty(shape, dtype=self._series.dtype, device=self._series.device)
@@ -88,6 +96,61 @@ class BezierSpline(InterpolationBase):
     method = "bez"
     min_times = 4
 
+    def __init__(self, series, t=None, differentiable=False, **kwargs):
+        if differentiable:
+            raise NotImplementedError("BezierSpline(differentiable=True): a BezierSpline is not a control path of cdeint, and the "
+                                      "history gathers give no gradient to the series; LinearInterpolation, CubicHermiteSpline and "
+                                      "NaturalCubicSpline take differentiable=True")
+        super().__init__(series, t, **kwargs)
+
+
+class _NaturalCoeffsFn(torch.autograd.Function):
+    """``Y, M = xde_spline_natural_coeffs(columns, knots)`` with the gradient to ``columns [B, Tn, C]``: one
+    xde_spline_natural_coeffs_backward launch (include/xde_hip_cdegrad.h (b)).  An unobserved entry gets ``+0``; the knots get none."""
+
+    @staticmethod
+    def forward(ctx, columns, knots):
+        Y, M = torch.empty_like(columns), torch.empty_like(columns)
+        _hip.get_backend()._spline_natural_coeffs(Y, M, columns, knots)
+        ctx.save_for_backward(columns, knots)
+        return Y, M
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gY, gM):
+        columns, knots = ctx.saved_tensors
+        g = torch.empty_like(columns)
+        _hip.get_backend()._spline_natural_coeffs_backward(g, gY.contiguous(), gM.contiguous(), columns, knots)
+        return g, None
+
+
+class _NaturalGatherFn(torch.autograd.Function):
+    """``val, der = xde_spline_natural_gather(Y, M, knots, tq)`` with the gradient to ``Y`` and ``M``: one
+    xde_spline_natural_gather_backward launch ((c) of the same header) over whichever of the two cotangents arrived."""
+
+    @staticmethod
+    def forward(ctx, Y, M, knots, tq):
+        shape = tuple(Y.shape[:-2]) + (tq.numel(), Y.shape[-1])
+        val = torch.empty(shape, dtype=Y.dtype, device=Y.device)
+        der = torch.empty_like(val)
+        _hip.get_backend()._spline_natural_gather(val, der, Y, M, knots, tq)
+        ctx.save_for_backward(knots, tq)
+        ctx.shape = tuple(Y.shape)
+        ctx.set_materialize_grads(False)
+        return val, der
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gval, gder):
+        if gval is None and gder is None:
+            return None, None, None, None
+        knots, tq = ctx.saved_tensors
+        gY = torch.empty(ctx.shape, dtype=knots.dtype, device=knots.device)
+        gM = torch.empty_like(gY)
+        cont = lambda g: None if g is None else g.contiguous()  # noqa: E731
+        _hip.get_backend()._spline_natural_gather_backward(gY, gM, cont(gval), cont(gder), knots, tq)
+        return gY, gM, None, None
+
 
 class NaturalCubicSpline(InterpolationBase):
     """The natural cubic spline through the observed entries of ``series [..., T, C]`` over strictly increasing ``t [T]`` (any spacing;
@@ -97,30 +160,41 @@ class NaturalCubicSpline(InterpolationBase):
 
     Construction runs one coefficient launch (xde_spline_natural_coeffs) after one host read that checks ``t`` and the columns;
     ``evaluate`` / ``derivative`` are one xde_spline_natural_gather launch, and give the bits the CDE contraction builds on chip.
-    ``_series`` holds the values on the full knot grid (missing entries filled from the spline), ``_coef`` the second derivatives."""
+    ``_series`` holds the values on the full knot grid (missing entries filled from the spline), ``_coef`` the second derivatives.
+
+    ``differentiable=True`` keeps the spline on ``series``' autograd graph (a control path of ``cdeint`` that comes from something
+    trained): ``Y`` and ``M`` then carry a gradient back to the observed entries of the series through one
+    xde_spline_natural_coeffs_backward launch per backward pass (unobserved entries get ``+0``), and ``evaluate`` / ``derivative`` are
+    differentiable through xde_spline_natural_gather_backward (include/xde_hip_cdegrad.h).  The knots get no gradient."""
 
     method = "natural"
     min_times = 2
 
-    def __init__(self, series, t=None, **kwargs):
-        super().__init__(series, t, **kwargs)
+    def __init__(self, series, t=None, differentiable=False, **kwargs):
+        super().__init__(series, t, differentiable, **kwargs)
         raw = self._series
         columns = raw.reshape((-1,) + tuple(raw.shape[-2:]))
         rising = (self._t[1:] > self._t[:-1]).all()  # (false for a NaN time too)
-        empty = torch.isnan(columns).all(dim=-2).any()
+        empty = torch.isnan(columns.detach()).all(dim=-2).any()
         rising, empty = torch.stack([rising, empty]).tolist()  # the one host read
         if not rising:
             raise ValueError("NaturalCubicSpline: t must be strictly increasing")
         if empty:
             raise ValueError("NaturalCubicSpline: a column of the series has no observed (non-NaN) value: there is nothing to "
                              "interpolate; drop the channel or fill it")
-        Y, M = torch.empty_like(columns), torch.empty_like(columns)
-        self._backend._spline_natural_coeffs(Y, M, columns, self._t)
+        if self.differentiable:
+            # Y and M stay on the series' graph: their cotangents flow back through ONE coefficient-backward launch per backward pass
+            Y, M = _NaturalCoeffsFn.apply(columns, self._t)
+        else:
+            Y, M = torch.empty_like(columns), torch.empty_like(columns)
+            self._backend._spline_natural_coeffs(Y, M, columns, self._t)
         self._series = Y.reshape(raw.shape)
         self._coef = M.reshape(raw.shape)
 
     def _gather(self, t):
         tq = torch.as_tensor(t).detach().to(device=self._series.device, dtype=self._series.dtype).contiguous().reshape(-1)
+        if self.differentiable:
+            return _NaturalGatherFn.apply(self._series, self._coef, self._t, tq)
         shape = tuple(self._series.shape[:-2]) + (tq.numel(), self._series.shape[-1])
         val = torch.empty(shape, dtype=self._series.dtype, device=self._series.device)
         der = torch.empty_like(val)

@@ -23,7 +23,7 @@ from .. import _hip
 from ..interpolation import BezierSpline, CubicHermiteSpline, InterpolationBase, LinearInterpolation, NaturalCubicSpline
 from .base_ode import BaseODE
 
-__all__ = ["BaseCDE", "CDEField", "CdeContractFn"]
+__all__ = ["BaseCDE", "CDEField", "CdeContractFn", "CdeControlContractFn"]
 
 
 class CdeContractFn(torch.autograd.Function):
@@ -58,6 +58,50 @@ class CdeContractFn(torch.autograd.Function):
         else:
             _hip.get_backend()._cde_contract_backward(gF, gout, series, knots, t, ctx.method)
         return gF, None, None, None, None, None
+
+
+class CdeControlContractFn(torch.autograd.Function):
+    """``CdeContractFn`` for a control that opted in with ``differentiable=True``: the same two launches give ``out`` and ``gF`` (the
+    same bits), and the control gets its cotangent too — ``gdX[b, c] = sum_h gout[b, h] F[b, h, c]`` scattered to the rows ``X'(t)``
+    read, one xde_cde_control_grad / _natural launch (include/xde_hip_cdegrad.h (a)) that runs only when the series (``Y`` and ``M``
+    for the natural control) asks for a gradient.  ``F`` is kept for it.  The knots and ``t`` get none."""
+
+    @staticmethod
+    def forward(ctx, F, series, knots, t, method, coef=None):
+        be = _hip.get_backend()
+        F = F.contiguous()
+        out = torch.empty(F.shape[:2], dtype=F.dtype, device=F.device)
+        if method == "natural":
+            be._cde_contract_natural(out, F, series, coef, knots, t)
+        else:
+            be._cde_contract(out, F, series, knots, t, method)
+        ctx.method, ctx.t_host = method, None if torch.is_tensor(t) else t
+        ctx.save_for_backward(F, series, knots, *([coef] if method == "natural" else []), *([t] if torch.is_tensor(t) else []))
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        F, series, knots, *rest = ctx.saved_tensors
+        coef = rest.pop(0) if ctx.method == "natural" else None
+        t = rest[0] if rest else ctx.t_host
+        be = _hip.get_backend()
+        gout = gout.contiguous()
+        gF = g_series = g_coef = None
+        if ctx.needs_input_grad[0]:
+            gF = torch.empty_like(F)
+            if coef is not None:
+                be._cde_contract_natural_backward(gF, gout, series, coef, knots, t)
+            else:
+                be._cde_contract_backward(gF, gout, series, knots, t, ctx.method)
+        if ctx.needs_input_grad[1] or (coef is not None and ctx.needs_input_grad[5]):
+            g_series = torch.empty_like(series)  # (every element is written by the launch: no memset)
+            if coef is not None:
+                g_coef = torch.empty_like(coef)
+                be._cde_control_grad_natural(g_series, g_coef, gout, F, knots, t)
+            else:
+                be._cde_control_grad(g_series, gout, F, knots, t, ctx.method)
+        return gF, g_series, None, None, None, g_coef
 
 
 def _kernel_time(t, series):
@@ -99,6 +143,15 @@ class CDEField(torch.nn.Module):
         d["_knots"] = X._t
         d["_method"] = X.method
         d["_coef"] = X._coef.reshape(d["_series"].shape) if isinstance(X, NaturalCubicSpline) else None
+        # a control built with differentiable=True goes through CdeControlContractFn; every other one through CdeContractFn, as before
+        d["_contract"] = CdeControlContractFn if getattr(X, "differentiable", False) else CdeContractFn
+
+    def control_tensors(self):
+        """The tensors of a differentiable control that ask for a gradient, as the contraction takes them: the series (linear /
+        cubic), ``Y`` and ``M`` (natural).  ``cdeint_adjoint`` appends them to the adjoint parameters.  Empty for any other control."""
+        if self._contract is not CdeControlContractFn:
+            return ()
+        return tuple(x for x in (self._series, self._coef) if x is not None and x.requires_grad)
 
     def forward(self, t, z):
         F = self.func(t, z)
@@ -116,7 +169,7 @@ class CDEField(torch.nn.Module):
             raise ValueError("z has leading dimensions {} and the control's series {}: they must be the same".format(
                 tuple(z.shape[:-1]), self._lead))
         H = z.shape[-1]
-        out = CdeContractFn.apply(F.reshape(-1, H, C), series, self._knots, _kernel_time(t, series), self._method, self._coef)
+        out = self._contract.apply(F.reshape(-1, H, C), series, self._knots, _kernel_time(t, series), self._method, self._coef)
         return out.reshape(z.shape)
 
 
