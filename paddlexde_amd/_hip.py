@@ -394,6 +394,11 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
+def _plan_dict(plan):
+    """A launch plan (the mirror of one of the headers' ``xde_*_plan_t``) as a dict of its fields."""
+    return {name: int(getattr(plan, name)) for name, _ in plan._fields_}
+
+
 def _dbl_array(xs):
     if isinstance(xs, C.Array):  # pre-marshalled by the caller (per-stage coefficient rows never change)
         return xs
@@ -997,7 +1002,7 @@ class HipBackend:
         xde_seam_plan_t's fields.  Nothing is enqueued."""
         plan = XdeSeamPlan()
         self._check(self.lib.xde_seam_plan(int(n), dtype_code(dtype), C.byref(plan)), "xde_seam_plan")
-        return {name: int(getattr(plan, name)) for name, _ in XdeSeamPlan._fields_}
+        return _plan_dict(plan)
 
     def _seam_state(self, ctrl):
         key = ctrl.data_ptr()
@@ -1034,42 +1039,55 @@ class HipBackend:
     # -- cdeint's vector field (include/xde_hip_cde.h) ----------------------------------------------------------------------------------
     # Private for the reason _interp_rows is: the public methods are the contract tests/_cpu_double.py mirrors.  Only CdeContractFn
     # (xde/base_cde.py) calls these.
-    def _cde_call(self, who, out, src, series, knots, t, method):
-        """One launch of ``xde<who>``: ``series [B, Tn, C]``, ``knots [Tn]``, the big operand ``[B, H, C]`` and the small one ``[B, H]``
-        contiguous on the device in one dtype; ``t`` a one-element float32 / float64 device tensor (read by the kernel: no host
-        synchronisation, and a captured launch replays with its current value) or a Python number."""
-        big, small = (src, out) if who == "_cde_contract" else (out, src)
-        self._require_device(out, src, series, knots)
-        if series.dim() != 3 or big.dim() != 3 or small.dim() != 2:
-            raise XdeError("{}: expected series [B, Tn, C], F [B, H, C] and out [B, H]".format(who))
-        B, Tn, C = series.shape
-        H = big.shape[1]
-        if tuple(big.shape) != (B, H, C) or tuple(small.shape) != (B, H) or tuple(knots.shape) != (Tn,):
-            raise XdeError("{}: shapes do not agree: series {}, knots {}, F {}, out {}".format(
-                who, tuple(series.shape), tuple(knots.shape), tuple(big.shape), tuple(small.shape)))
-        for x in (out, src, series, knots):
-            if not x.is_contiguous() or x.dtype != series.dtype or x.device != series.device:
-                raise XdeError("{}: the operands must be contiguous tensors of one dtype on one device".format(who))
-        if torch.is_tensor(t):
-            self._require_device(t)
-            if t.numel() != 1 or t.dtype not in (torch.float32, torch.float64) or t.device != series.device:
-                raise XdeError("{}: t must be ONE float32 / float64 element on the series' device (got shape {}, {}, {})".format(
-                    who, tuple(t.shape), t.dtype, t.device))
-            t_dev, t_host, tt = t.data_ptr(), 0.0, dtype_code(t.dtype)
+    def _launch_time(self, who, t, like):
+        """``t`` as a launch takes it, ``(t_dev, t_host, time_dtype)``: ONE float32 / float64 element on ``like``'s device (read by the
+        kernel: no host synchronisation, and a captured launch replays with its current value) or a Python number."""
+        if not torch.is_tensor(t):
+            return None, float(t), XDE_F64
+        self._require_device(t)
+        if t.numel() != 1 or t.dtype not in (torch.float32, torch.float64) or t.device != like.device:
+            raise XdeError("{}: t must be ONE float32 / float64 element on the series' device (got shape {}, {}, {})".format(
+                who, tuple(t.shape), t.dtype, t.device))
+        return t.data_ptr(), 0.0, dtype_code(t.dtype)
+
+    def _cde_launch(self, who, out, src, series, coef, knots, t, method):
+        """One launch of ``xde<who>``: the control's rows ``[B, Tn, C]`` — ``series`` of the ``method`` spline, or ``series, coef`` = ``Y,
+        M`` of the natural control (``method`` None) — ``knots [Tn]``, the big operand ``[B, H, C]`` (``out`` of a ``_backward``, else
+        ``src``) and the small one ``[B, H]`` contiguous on one device in one dtype; ``t`` as ``_launch_time`` takes it."""
+        natural = coef is not None
+        big, small = (out, src) if who.endswith("_backward") else (src, out)
+        if natural:
+            self._spline_operands(who, out, src, series, coef, knots)
         else:
-            t_dev, t_host, tt = None, float(t), XDE_F64
-        rc = getattr(self.lib, "xde" + who)(out.data_ptr(), src.data_ptr(), series.data_ptr(), knots.data_ptr(), t_dev, t_host, tt, B, H, C,
-                                            Tn, HISTORY_METHODS[method], dtype_code(series.dtype), self._stream(series))
-        self._check(rc, "xde" + who)
+            self._spline_operands(who, out, src, series, knots)
+        if series.dim() != 3 or big.dim() != 3 or small.dim() != 2:
+            raise XdeError("{}: expected {} [B, Tn, C], F [B, H, C] and out [B, H]".format(who, "Y, M" if natural else "series"))
+        B, Tn, C_ = series.shape
+        H = big.shape[1]
+        agree = tuple(big.shape) == (B, H, C_) and tuple(small.shape) == (B, H) and tuple(knots.shape) == (Tn,)
+        if not agree or (natural and coef.shape != series.shape):
+            rows = "Y {}, M {}".format(tuple(series.shape), tuple(coef.shape)) if natural else "series {}".format(tuple(series.shape))
+            raise XdeError("{}: shapes do not agree: {}, knots {}, F {}, out {}".format(
+                who, rows, tuple(knots.shape), tuple(big.shape), tuple(small.shape)))
+        t_dev, t_host, tt = self._launch_time(who, t, series)
+        sym = "xde" + who
+        fn, dt, st = getattr(self.lib, sym), dtype_code(series.dtype), self._stream(series)
+        if natural:
+            rc = fn(out.data_ptr(), src.data_ptr(), series.data_ptr(), coef.data_ptr(), knots.data_ptr(), t_dev, t_host, tt, B, H, C_, Tn,
+                    dt, st)
+        else:
+            rc = fn(out.data_ptr(), src.data_ptr(), series.data_ptr(), knots.data_ptr(), t_dev, t_host, tt, B, H, C_, Tn,
+                    HISTORY_METHODS[method], dt, st)
+        self._check(rc, sym)
 
     def _cde_contract(self, out, F, series, knots, t, method):
         """``out[b, h] = sum_c F[b, h, c] * dX[b, c]`` with ``dX`` the derivative at ``t`` of the ``method`` ("linear" | "cubic") spline
         through ``series`` over ``knots``, in the summation order of include/xde_hip_cde.h.  One launch; dX is never written."""
-        self._cde_call("_cde_contract", out, F, series, knots, t, method)
+        self._cde_launch("_cde_contract", out, F, series, None, knots, t, method)
 
     def _cde_contract_backward(self, gF, gout, series, knots, t, method):
         """``gF[b, h, c] = gout[b, h] * dX[b, c]``: the cotangent of ``_cde_contract``'s F.  One launch."""
-        self._cde_call("_cde_contract_backward", gF, gout, series, knots, t, method)
+        self._cde_launch("_cde_contract_backward", gF, gout, series, None, knots, t, method)
 
     def _cde_plan(self, backward, big, B, H, channels):
         """The launch plan of ``_cde_contract`` (``backward`` false: ``big`` is F) or ``_cde_contract_backward`` (``big`` is gF) for
@@ -1077,7 +1095,7 @@ class HipBackend:
         plan = XdeCdePlan()
         rc = self.lib.xde_cde_plan(int(bool(backward)), big.data_ptr(), int(B), int(H), int(channels), dtype_code(big.dtype), C.byref(plan))
         self._check(rc, "xde_cde_plan")
-        return {name: int(getattr(plan, name)) for name, _ in XdeCdePlan._fields_}
+        return _plan_dict(plan)
 
     # -- the natural cubic spline control (include/xde_hip_spline.h) -------------------------------------------------------------------
     # Private for the reason the _cde_* methods are.  NaturalCubicSpline (interpolation) and CdeContractFn (xde/base_cde.py) call these.
@@ -1117,41 +1135,22 @@ class HipBackend:
                                                 Y.numel() // (Tn * D), Tn, tq.numel(), D, dtype_code(Y.dtype), self._stream(Y))
         self._check(rc, "xde_spline_natural_gather")
 
-    def _cde_natural_call(self, who, out, src, Y, M, knots, t):
-        big, small = (src, out) if who == "_cde_contract_natural" else (out, src)
-        self._spline_operands(who, out, src, Y, M, knots)
-        if Y.dim() != 3 or big.dim() != 3 or small.dim() != 2:
-            raise XdeError("{}: expected Y, M [B, Tn, C], F [B, H, C] and out [B, H]".format(who))
-        B, Tn, C_ = Y.shape
-        H = big.shape[1]
-        if tuple(big.shape) != (B, H, C_) or tuple(small.shape) != (B, H) or tuple(knots.shape) != (Tn,) or M.shape != Y.shape:
-            raise XdeError("{}: shapes do not agree: Y {}, M {}, knots {}, F {}, out {}".format(
-                who, tuple(Y.shape), tuple(M.shape), tuple(knots.shape), tuple(big.shape), tuple(small.shape)))
-        if torch.is_tensor(t):
-            self._require_device(t)
-            if t.numel() != 1 or t.dtype not in (torch.float32, torch.float64) or t.device != Y.device:
-                raise XdeError("{}: t must be ONE float32 / float64 element on the series' device (got shape {}, {}, {})".format(
-                    who, tuple(t.shape), t.dtype, t.device))
-            t_dev, t_host, tt = t.data_ptr(), 0.0, dtype_code(t.dtype)
-        else:
-            t_dev, t_host, tt = None, float(t), XDE_F64
-        rc = getattr(self.lib, "xde" + who)(out.data_ptr(), src.data_ptr(), Y.data_ptr(), M.data_ptr(), knots.data_ptr(), t_dev, t_host, tt,
-                                            B, H, C_, Tn, dtype_code(Y.dtype), self._stream(Y))
-        self._check(rc, "xde" + who)
-
     def _cde_contract_natural(self, out, F, Y, M, knots, t):
         """``_cde_contract`` with ``dX`` the derivative at ``t`` of the natural cubic spline ``(Y, M, knots)``.  One launch."""
-        self._cde_natural_call("_cde_contract_natural", out, F, Y, M, knots, t)
+        self._cde_launch("_cde_contract_natural", out, F, Y, M, knots, t, None)
 
     def _cde_contract_natural_backward(self, gF, gout, Y, M, knots, t):
         """``gF[b, h, c] = gout[b, h] * dX[b, c]``: the cotangent of ``_cde_contract_natural``'s F.  One launch."""
-        self._cde_natural_call("_cde_contract_natural_backward", gF, gout, Y, M, knots, t)
+        self._cde_launch("_cde_contract_natural_backward", gF, gout, Y, M, knots, t, None)
 
     # -- the gradient with respect to the control path (include/xde_hip_cdegrad.h) -----------------------------------------------------
     # Private for the reason the _cde_* methods are.  CdeControlContractFn (xde/base_cde.py) and the differentiable splines
     # (interpolation) call these.
-    def _cde_grad_operands(self, who, outs, gout, F, knots, t, Tn):
+    def _cde_grad_launch(self, who, outs, gout, F, knots, t, method):
+        """One launch of ``xde<who>``: the control's cotangents ``outs`` (each ``[B, Tn, C]``), ``gout [B, H]``, ``F [B, H, C]`` and ``knots
+        [Tn]`` contiguous on one device in one dtype; ``t`` as ``_launch_time`` takes it; ``method`` None for the natural control."""
         self._spline_operands(who, *outs, gout, F, knots)
+        Tn = outs[0].shape[1] if outs[0].dim() == 3 else -1
         if F.dim() != 3 or gout.dim() != 2 or tuple(gout.shape) != tuple(F.shape[:2]) or tuple(knots.shape) != (Tn,):
             raise XdeError("{}: expected gout [B, H], F [B, H, C] and knots [Tn], got {}, {}, {}".format(
                 who, tuple(gout.shape), tuple(F.shape), tuple(knots.shape)))
@@ -1159,31 +1158,23 @@ class HipBackend:
         for o in outs:
             if tuple(o.shape) != (B, Tn, C_):
                 raise XdeError("{}: the control's cotangent must be [B, Tn, C] = {}, got {}".format(who, (B, Tn, C_), tuple(o.shape)))
-        if torch.is_tensor(t):
-            self._require_device(t)
-            if t.numel() != 1 or t.dtype not in (torch.float32, torch.float64) or t.device != F.device:
-                raise XdeError("{}: t must be ONE float32 / float64 element on the series' device (got shape {}, {}, {})".format(
-                    who, tuple(t.shape), t.dtype, t.device))
-            return B, H, C_, t.data_ptr(), 0.0, dtype_code(t.dtype)
-        return B, H, C_, None, float(t), XDE_F64
+        t_dev, t_host, tt = self._launch_time(who, t, F)
+        tail = (dtype_code(F.dtype), self._stream(F))
+        if method is not None:
+            tail = (HISTORY_METHODS[method],) + tail
+        rc = getattr(self.lib, "xde" + who)(*[o.data_ptr() for o in outs], gout.data_ptr(), F.data_ptr(), knots.data_ptr(), t_dev, t_host,
+                                            tt, B, H, C_, Tn, *tail)
+        self._check(rc, "xde" + who)
 
     def _cde_control_grad(self, gSeries, gout, F, knots, t, method):
         """``gSeries[b, k, c]``: the cotangent of the ``method`` ("linear" | "cubic") control's series in ``_cde_contract``, from ``gout
         [B, H]`` and ``F [B, H, C]`` — ``gdX = sum_h gout * F`` scattered to the rows ``X'(t)`` read, ``+0`` elsewhere.  One launch that
         writes every element of ``gSeries`` once."""
-        who = "_cde_control_grad"
-        B, H, C_, t_dev, t_host, tt = self._cde_grad_operands(who, (gSeries,), gout, F, knots, t, gSeries.shape[1] if gSeries.dim() == 3 else -1)
-        rc = self.lib.xde_cde_control_grad(gSeries.data_ptr(), gout.data_ptr(), F.data_ptr(), knots.data_ptr(), t_dev, t_host, tt, B, H, C_,
-                                           gSeries.shape[1], HISTORY_METHODS[method], dtype_code(F.dtype), self._stream(F))
-        self._check(rc, "xde_cde_control_grad")
+        self._cde_grad_launch("_cde_control_grad", (gSeries,), gout, F, knots, t, method)
 
     def _cde_control_grad_natural(self, gY, gM, gout, F, knots, t):
         """``gY, gM [B, Tn, C]``: the cotangents of the natural control's ``Y`` and ``M`` in ``_cde_contract_natural``.  One launch."""
-        who = "_cde_control_grad_natural"
-        B, H, C_, t_dev, t_host, tt = self._cde_grad_operands(who, (gY, gM), gout, F, knots, t, gY.shape[1] if gY.dim() == 3 else -1)
-        rc = self.lib.xde_cde_control_grad_natural(gY.data_ptr(), gM.data_ptr(), gout.data_ptr(), F.data_ptr(), knots.data_ptr(), t_dev,
-                                                   t_host, tt, B, H, C_, gY.shape[1], dtype_code(F.dtype), self._stream(F))
-        self._check(rc, "xde_cde_control_grad_natural")
+        self._cde_grad_launch("_cde_control_grad_natural", (gY, gM), gout, F, knots, t, None)
 
     def _cde_control_grad_plan(self, F, B, H, channels):
         """The launch plan of ``_cde_control_grad`` / ``_natural`` for ``[B, H, channels]``, ``F``'s dtype and its alignment, as a dict
@@ -1191,7 +1182,7 @@ class HipBackend:
         plan = XdeCdeGradPlan()
         rc = self.lib.xde_cde_control_grad_plan(F.data_ptr(), int(B), int(H), int(channels), dtype_code(F.dtype), C.byref(plan))
         self._check(rc, "xde_cde_control_grad_plan")
-        return {name: int(getattr(plan, name)) for name, _ in XdeCdeGradPlan._fields_}
+        return _plan_dict(plan)
 
     def _spline_natural_coeffs_backward(self, gSeries, gY, gM, series, knots):
         """``gSeries [B, Tn, C]`` from the cotangents ``gY, gM`` of ``_spline_natural_coeffs``'s outputs: its transpose.  ``series`` is

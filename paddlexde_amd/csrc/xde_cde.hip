@@ -18,6 +18,7 @@
 #include "xde_hip_spline.h"
 
 #include "xde_common.hpp"
+#include "xde_control_host.hpp"
 #include "xde_spline_device.hpp"
 
 using namespace xde;
@@ -26,7 +27,6 @@ namespace {
 
 constexpr int kCdeMaxC = 2048;  // channels of dX[b, :] a workgroup keeps in LDS (16 KiB of fp64); a longer row is recomputed per use
 constexpr int kCdeRows = 4;     // rows of F a team has in flight (independent 16-byte loads per lane)
-constexpr int kCdeNatural = 3;  // CdeArgs::method of the natural control (xde_hip_spline.h); the XDE_HISTORY_* codes are 0..2
 
 struct CdeArgs {
   void* out;         // out[B, H]   | gF[B, H, C]
@@ -62,9 +62,7 @@ struct CdeTab<T, true> {
 // the launch's time -> the query's table entry (one thread per workgroup)
 template <typename T, bool NAT>
 __device__ __forceinline__ void cde_make_tab(CdeTab<T, NAT>* tb, const CdeArgs& a) {
-  double t = a.t_host;
-  if (a.t_dev) t = a.time_f64 ? *static_cast<const double*>(a.t_dev) : double(*static_cast<const float*>(a.t_dev));
-  const T tau = T(t);  // the time in the series dtype first (InterpolationBase._gather)
+  const T tau = T(launch_time(a.t_dev, a.time_f64, a.t_host));  // the time in the series dtype first (InterpolationBase._gather)
   const T* ts = static_cast<const T*>(a.knots);
   if constexpr (NAT) {
     tb->nat = make_natural_lag<T>(ts, tau, a.Tn);
@@ -285,32 +283,6 @@ __global__ __launch_bounds__(kBlock) void xde_cde_backward_kernel(CdeArgs a) {
   }
 }
 
-int pow2ceil(int x) {
-  int r = 1;
-  while (r < x) r <<= 1;
-  return r;
-}
-
-// (`coef`: M of the natural control, method kCdeNatural — the public method codes are checked for the other entry points; else `series`)
-int cde_check(const std::string& who, const void* out, const void* in, const void* series, const void* coef, const void* knots,
-              const void* t_dev, int time_dtype, int64_t B, int H, int C, int Tn, int method, int dtype) {
-  if (!out || !in || !series || !coef || !knots) return fail(XDE_EBADARG, who + ": null pointer");
-  if (B < 1 || H < 1 || C < 1) return fail(XDE_EBADARG, who + ": bad sizes (need B, H, C >= 1)");
-  if (Tn < 2) return fail(XDE_EBADARG, who + ": bad sizes (need Tn >= 2)");
-  if (dtype != XDE_F32 && dtype != XDE_F64) return fail(XDE_EBADARG, who + ": bad dtype");
-  if (time_dtype != XDE_F32 && time_dtype != XDE_F64) return fail(XDE_EBADARG, who + ": bad time_dtype");
-  if (method == XDE_HISTORY_BEZIER)
-    return fail(XDE_EBADARG, who + ": XDE_HISTORY_BEZIER is not a control path (its four-row window does not pass through the data); "
-                                   "XDE_HISTORY_LINEAR and XDE_HISTORY_CUBIC are served");
-  if (method != XDE_HISTORY_LINEAR && method != XDE_HISTORY_CUBIC && method != kCdeNatural) return fail(XDE_EBADARG, who + ": unknown method");
-  const uintptr_t em = dtype == XDE_F32 ? 3u : 7u, tm = time_dtype == XDE_F32 ? 3u : 7u;
-  const void* ps[5] = {out, in, series, coef, knots};
-  for (const void* p : ps)
-    if (reinterpret_cast<uintptr_t>(p) & em) return fail(XDE_EBADARG, who + ": operand not aligned to its element type");
-  if (t_dev && (reinterpret_cast<uintptr_t>(t_dev) & tm)) return fail(XDE_EBADARG, who + ": t_dev not aligned to its element type");
-  return XDE_OK;
-}
-
 // slices of H per batch row: one (a workgroup reads series[b] once) unless B alone leaves most of the chip idle
 void cde_slices(xde_cde_plan_t* p, int64_t B, int H, int C, int64_t rows_per_pass, int64_t full_pass) {
   constexpr int64_t kWant = 1024;  // work items that fill the chip
@@ -334,7 +306,7 @@ void cde_slices(xde_cde_plan_t* p, int64_t B, int H, int C, int64_t rows_per_pas
 // everything the host decides about a launch, from the direction, the sizes, the dtype and the big operand's alignment: the ONE
 // statement of it — the launchers run what it returns, xde_cde_plan reports it
 xde_cde_plan_t cde_plan(bool backward, const void* big, int64_t B, int H, int C, int dtype) {
-  const int width = dtype == XDE_F32 ? 4 : 2;
+  const int width = vec_width(dtype);
   xde_cde_plan_t p;
   memset(&p, 0, sizeof(p));
   p.vec = (C % width) == 0 && aligned16(big);
@@ -360,52 +332,45 @@ xde_cde_plan_t cde_plan(bool backward, const void* big, int64_t B, int H, int C,
 }
 
 void cde_args(CdeArgs* a, const xde_cde_plan_t& p, void* out, const void* in, const void* series, const void* coef, const void* knots,
-              const void* t_dev, double t_host, int time_dtype, int64_t B, int H, int C, int Tn, int method) {
+              const TimedCall& c) {
   memset(a, 0, sizeof(*a));
-  a->out = out, a->in = in, a->series = series, a->coef = coef, a->knots = knots, a->t_dev = t_dev, a->t_host = t_host;
-  a->B = B, a->H = H, a->C = C, a->Tn = Tn, a->method = method, a->time_f64 = time_dtype == XDE_F64;
+  a->out = out, a->in = in, a->series = series, a->coef = coef, a->knots = knots, a->t_dev = c.t_dev, a->t_host = c.t_host;
+  a->B = c.B, a->H = c.H, a->C = c.C, a->Tn = c.Tn, a->method = c.method, a->time_f64 = c.time_dtype == XDE_F64;
   a->R = p.R;
   for (a->r_log = 0; (1 << a->r_log) < a->R; ++a->r_log) {}
   a->S = p.S, a->Hc = p.Hc, a->Gb = p.Gb, a->lds = p.lds, a->nt = p.nt;
 }
 
-// (a launch that groups batch rows keeps their dX rows in LDS: GRP implies LDSDX)
-#define CDE_DISPATCH_(KERNEL, TY, NAT)                                                                    \
-  do {                                                                                                    \
-    if (p.vec) {                                                                                          \
-      if (p.grouped) XDE_LAUNCH((KERNEL<TY, true, true, true, NAT>), g, blk, st, prof, a);                \
-      else if (p.lds) XDE_LAUNCH((KERNEL<TY, true, true, false, NAT>), g, blk, st, prof, a);              \
-      else XDE_LAUNCH((KERNEL<TY, true, false, false, NAT>), g, blk, st, prof, a);                        \
-    } else {                                                                                              \
-      if (p.grouped) XDE_LAUNCH((KERNEL<TY, false, true, true, NAT>), g, blk, st, prof, a);               \
-      else if (p.lds) XDE_LAUNCH((KERNEL<TY, false, true, false, NAT>), g, blk, st, prof, a);             \
-      else XDE_LAUNCH((KERNEL<TY, false, false, false, NAT>), g, blk, st, prof, a);                       \
-    }                                                                                                     \
-  } while (0)
-#define CDE_DISPATCH(KERNEL, TY)                             \
-  do {                                                       \
-    if (method == kCdeNatural) CDE_DISPATCH_(KERNEL, TY, true); \
-    else CDE_DISPATCH_(KERNEL, TY, false);                   \
-  } while (0)
-
-// the one launcher of both directions and every control: `who` has passed cde_check
-int cde_launch(bool backward, void* out, const void* in, const void* series, const void* coef, const void* knots, const void* t_dev,
-               double t_host, int time_dtype, int64_t B, int H, int C, int Tn, int method, int dtype, void* stream) {
-  const xde_cde_plan_t p = cde_plan(backward, backward ? out : in, B, H, C, dtype);
+// the one launcher of both directions and every control: the arguments have passed check_timed (`coef`: M of the natural control,
+// method kMethodNatural; else `series` again, never read)
+int cde_launch(bool backward, void* out, const void* in, const void* series, const void* coef, const void* knots, const TimedCall& c) {
+  const xde_cde_plan_t p = cde_plan(backward, backward ? out : in, c.B, c.H, c.C, c.dtype);
   CdeArgs a;
-  cde_args(&a, p, out, in, series, coef, knots, t_dev, t_host, time_dtype, B, H, C, Tn, method);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const double es = dtype == XDE_F32 ? 4.0 : 8.0;
-  const double rows = method == kCdeNatural ? 4.0 : 3.0;  // control rows read per batch row
-  ProfScope prof(XDE_KID_DENSE, (double(B) * H * C + double(B) * H + rows * double(B) * C) * es);
+  cde_args(&a, p, out, in, series, coef, knots, c);
+  hipStream_t st = static_cast<hipStream_t>(c.stream);
+  const bool natural = c.method == kMethodNatural;
+  const double rows = natural ? 4.0 : 3.0;  // control rows read per batch row
+  ProfScope prof(XDE_KID_DENSE, (double(c.B) * c.H * c.C + double(c.B) * c.H + rows * double(c.B) * c.C) * elem_size(c.dtype));
   dim3 g(static_cast<unsigned>(p.blocks)), blk(kBlock);
-  if (!backward) {
-    if (dtype == XDE_F32) CDE_DISPATCH(xde_cde_contract_kernel, float);
-    else CDE_DISPATCH(xde_cde_contract_kernel, double);
-  } else {
-    if (dtype == XDE_F32) CDE_DISPATCH(xde_cde_backward_kernel, float);
-    else CDE_DISPATCH(xde_cde_backward_kernel, double);
-  }
+  with_flag(!backward, [&](auto forward) {
+    with_dtype(c.dtype, [&](auto ty) {
+      using T = typename decltype(ty)::type;
+      with_flag(natural, [&](auto nat) {
+        with_flag(p.vec != 0, [&](auto vec) {
+          auto launch = [&](auto ldsdx, auto grp) {
+            constexpr bool VEC = decltype(vec)::value, LDSDX = decltype(ldsdx)::value, GRP = decltype(grp)::value;
+            constexpr bool NAT = decltype(nat)::value;
+            if constexpr (decltype(forward)::value) XDE_LAUNCH((xde_cde_contract_kernel<T, VEC, LDSDX, GRP, NAT>), g, blk, st, prof, a);
+            else XDE_LAUNCH((xde_cde_backward_kernel<T, VEC, LDSDX, GRP, NAT>), g, blk, st, prof, a);
+          };
+          // (a launch that groups batch rows keeps their dX rows in LDS: GRP implies LDSDX, so <LDSDX = false, GRP = true> does not exist)
+          if (p.grouped) launch(std::true_type{}, std::true_type{});
+          else if (p.lds) launch(std::true_type{}, std::false_type{});
+          else launch(std::false_type{}, std::false_type{});
+        });
+      });
+    });
+  });
   HIP_TRY(hipGetLastError());
   return XDE_OK;
 }
@@ -416,37 +381,34 @@ extern "C" {
 
 int xde_cde_contract(void* out, const void* F, const void* series, const void* knots, const void* t_dev, double t_host, int time_dtype,
                      int64_t B, int H, int C, int Tn, int method, int dtype, void* stream) {
-  if (method == kCdeNatural) return fail(XDE_EBADARG, "xde_cde_contract: unknown method");
-  if (int rc = cde_check("xde_cde_contract", out, F, series, series, knots, t_dev, time_dtype, B, H, C, Tn, method, dtype)) return rc;
-  return cde_launch(false, out, F, series, series, knots, t_dev, t_host, time_dtype, B, H, C, Tn, method, dtype, stream);
+  const TimedCall c{t_dev, t_host, time_dtype, B, H, C, Tn, method, dtype, stream};
+  if (int rc = check_timed(ArgCheck{"xde_cde_contract"}.public_method(method), {out, F, series, knots}, c)) return rc;
+  return cde_launch(false, out, F, series, series, knots, c);
 }
 
 int xde_cde_contract_backward(void* gF, const void* gout, const void* series, const void* knots, const void* t_dev, double t_host,
                               int time_dtype, int64_t B, int H, int C, int Tn, int method, int dtype, void* stream) {
-  if (method == kCdeNatural) return fail(XDE_EBADARG, "xde_cde_contract_backward: unknown method");
-  if (int rc = cde_check("xde_cde_contract_backward", gF, gout, series, series, knots, t_dev, time_dtype, B, H, C, Tn, method, dtype)) return rc;
-  return cde_launch(true, gF, gout, series, series, knots, t_dev, t_host, time_dtype, B, H, C, Tn, method, dtype, stream);
+  const TimedCall c{t_dev, t_host, time_dtype, B, H, C, Tn, method, dtype, stream};
+  if (int rc = check_timed(ArgCheck{"xde_cde_contract_backward"}.public_method(method), {gF, gout, series, knots}, c)) return rc;
+  return cde_launch(true, gF, gout, series, series, knots, c);
 }
 
 int xde_cde_contract_natural(void* out, const void* F, const void* Y, const void* M, const void* knots, const void* t_dev, double t_host,
                              int time_dtype, int64_t B, int H, int C, int Tn, int dtype, void* stream) {
-  if (int rc = cde_check("xde_cde_contract_natural", out, F, Y, M, knots, t_dev, time_dtype, B, H, C, Tn, kCdeNatural, dtype)) return rc;
-  return cde_launch(false, out, F, Y, M, knots, t_dev, t_host, time_dtype, B, H, C, Tn, kCdeNatural, dtype, stream);
+  const TimedCall c{t_dev, t_host, time_dtype, B, H, C, Tn, kMethodNatural, dtype, stream};
+  if (int rc = check_timed({"xde_cde_contract_natural"}, {out, F, Y, M, knots}, c)) return rc;
+  return cde_launch(false, out, F, Y, M, knots, c);
 }
 
 int xde_cde_contract_natural_backward(void* gF, const void* gout, const void* Y, const void* M, const void* knots, const void* t_dev,
                                       double t_host, int time_dtype, int64_t B, int H, int C, int Tn, int dtype, void* stream) {
-  if (int rc = cde_check("xde_cde_contract_natural_backward", gF, gout, Y, M, knots, t_dev, time_dtype, B, H, C, Tn, kCdeNatural, dtype))
-    return rc;
-  return cde_launch(true, gF, gout, Y, M, knots, t_dev, t_host, time_dtype, B, H, C, Tn, kCdeNatural, dtype, stream);
+  const TimedCall c{t_dev, t_host, time_dtype, B, H, C, Tn, kMethodNatural, dtype, stream};
+  if (int rc = check_timed({"xde_cde_contract_natural_backward"}, {gF, gout, Y, M, knots}, c)) return rc;
+  return cde_launch(true, gF, gout, Y, M, knots, c);
 }
 
 int xde_cde_plan(int backward, const void* big, int64_t B, int H, int C, int dtype, xde_cde_plan_t* plan) {
-  if (!plan) return fail(XDE_EBADARG, "xde_cde_plan: null pointer");
-  if (B < 1 || H < 1 || C < 1) return fail(XDE_EBADARG, "xde_cde_plan: bad sizes (need B, H, C >= 1)");
-  if (dtype != XDE_F32 && dtype != XDE_F64) return fail(XDE_EBADARG, "xde_cde_plan: bad dtype");
-  if (reinterpret_cast<uintptr_t>(big) & (dtype == XDE_F32 ? 3u : 7u))
-    return fail(XDE_EBADARG, "xde_cde_plan: operand not aligned to its element type");
+  if (int rc = ArgCheck{"xde_cde_plan"}.not_null({plan}).sizes("B, H, C", {B, H, C}).dtype(dtype).aligned({big}, dtype).rc) return rc;
   *plan = cde_plan(backward != 0, big, B, H, C, dtype);
   return XDE_OK;
 }

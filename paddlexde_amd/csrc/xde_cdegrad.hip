@@ -12,6 +12,7 @@
 #include "xde_hip_cdegrad.h"
 
 #include "xde_common.hpp"
+#include "xde_control_host.hpp"
 #include "xde_spline_device.hpp"
 
 using namespace xde;
@@ -20,7 +21,6 @@ namespace {
 
 constexpr int kGradMaxP = 32;   // partial sums over h per channel
 constexpr int kGradEntries = 6;  // (row, weight) entries of dX's transpose: 2 linear, 6 cubic, 2 + 2 natural
-constexpr int kGradNatural = 3;  // GradArgs::method of the natural control; the XDE_HISTORY_* codes are 0..2
 constexpr int kGatherTile = 128;  // query times per table of the gather's transpose
 
 struct GradArgs {
@@ -69,9 +69,7 @@ __device__ __forceinline__ void natural_val_weights(T h, T s, T* w) {
 // the launch's time -> the entries of dX's transpose (one thread per workgroup)
 template <typename T, bool NAT>
 __device__ __forceinline__ void grad_make_tab(GradTab<T>* tb, const GradArgs& a) {
-  double t = a.t_host;
-  if (a.t_dev) t = a.time_f64 ? *static_cast<const double*>(a.t_dev) : double(*static_cast<const float*>(a.t_dev));
-  const T tau = T(t);
+  const T tau = T(launch_time(a.t_dev, a.time_f64, a.t_host));
   const T* ts = static_cast<const T*>(a.knots);
   const int Tn = a.Tn;
   tb->n[0] = tb->n[1] = 0;
@@ -349,17 +347,9 @@ __global__ __launch_bounds__(kBlock) void xde_natural_gather_backward_kernel(T* 
   }
 }
 
-int pow2ceil(int x) {
-  int r = 1;
-  while (r < x) r <<= 1;
-  return r;
-}
-
-bool misaligned(const void* p, int dtype) { return (reinterpret_cast<uintptr_t>(p) & (dtype == XDE_F32 ? 3u : 7u)) != 0; }
-
 // everything the host decides about a launch of (a): the ONE statement of it — the launcher runs it, the plan query reports it
 xde_cdegrad_plan_t grad_plan(const void* F, int64_t B, int H, int C, int dtype) {
-  const int width = dtype == XDE_F32 ? 4 : 2;
+  const int width = vec_width(dtype);
   xde_cdegrad_plan_t p;
   memset(&p, 0, sizeof(p));
   p.vec = (C % width) == 0 && aligned16(F);
@@ -373,48 +363,34 @@ xde_cdegrad_plan_t grad_plan(const void* F, int64_t B, int H, int C, int dtype) 
   return p;
 }
 
-// (`out1`: gM of the natural control, method kGradNatural; else null)
-int grad_launch(const std::string& who, void* out0, void* out1, const void* gout, const void* F, const void* knots, const void* t_dev,
-                double t_host, int time_dtype, int64_t B, int H, int C, int Tn, int method, int dtype, void* stream) {
-  const bool nat = method == kGradNatural;
-  if (!out0 || (nat && !out1) || !gout || !F || !knots) return fail(XDE_EBADARG, who + ": null pointer");
-  if (B < 1 || H < 1 || C < 1) return fail(XDE_EBADARG, who + ": bad sizes (need B, H, C >= 1)");
-  if (Tn < 2) return fail(XDE_EBADARG, who + ": bad sizes (need Tn >= 2)");
-  if (dtype != XDE_F32 && dtype != XDE_F64) return fail(XDE_EBADARG, who + ": bad dtype");
-  if (time_dtype != XDE_F32 && time_dtype != XDE_F64) return fail(XDE_EBADARG, who + ": bad time_dtype");
-  if (method == XDE_HISTORY_BEZIER)
-    return fail(XDE_EBADARG, who + ": XDE_HISTORY_BEZIER is not a control path (its four-row window does not pass through the data); "
-                                   "XDE_HISTORY_LINEAR and XDE_HISTORY_CUBIC are served");
-  if (method != XDE_HISTORY_LINEAR && method != XDE_HISTORY_CUBIC && !nat) return fail(XDE_EBADARG, who + ": unknown method");
-  const void* ps[5] = {out0, out1, gout, F, knots};
-  for (const void* p : ps)
-    if (misaligned(p, dtype)) return fail(XDE_EBADARG, who + ": operand not aligned to its element type");
-  if (t_dev && misaligned(t_dev, time_dtype)) return fail(XDE_EBADARG, who + ": t_dev not aligned to its element type");
-  const xde_cdegrad_plan_t p = grad_plan(F, B, H, C, dtype);
+void grad_args(GradArgs* a, const xde_cdegrad_plan_t& p, void* out0, void* out1, const void* gout, const void* F, const void* knots,
+               const TimedCall& c) {
+  memset(a, 0, sizeof(*a));
+  a->out0 = out0, a->out1 = out1, a->gout = gout, a->F = F, a->knots = knots, a->t_dev = c.t_dev, a->t_host = c.t_host;
+  a->B = c.B, a->H = c.H, a->C = c.C, a->Tn = c.Tn, a->method = c.method, a->time_f64 = c.time_dtype == XDE_F64;
+  a->P = p.P;
+  for (a->p_log = 0; (1 << a->p_log) < a->P; ++a->p_log) {}
+  a->ovec = p.vec && aligned16(out0) && aligned16(out1);
+}
+
+// the one launcher of both controls: the arguments have passed check_timed (`out1`: gM of the natural control, else null)
+int grad_launch(void* out0, void* out1, const void* gout, const void* F, const void* knots, const TimedCall& c) {
+  const xde_cdegrad_plan_t p = grad_plan(F, c.B, c.H, c.C, c.dtype);
   GradArgs a;
-  memset(&a, 0, sizeof(a));
-  a.out0 = out0, a.out1 = out1, a.gout = gout, a.F = F, a.knots = knots, a.t_dev = t_dev, a.t_host = t_host;
-  a.B = B, a.H = H, a.C = C, a.Tn = Tn, a.method = method, a.time_f64 = time_dtype == XDE_F64;
-  a.P = p.P;
-  a.ovec = p.vec && aligned16(out0) && aligned16(out1);
-  for (a.p_log = 0; (1 << a.p_log) < a.P; ++a.p_log) {}
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const double es = dtype == XDE_F32 ? 4.0 : 8.0;
-  ProfScope prof(XDE_KID_DENSE, (double(B) * H * C + double(B) * H + (nat ? 2.0 : 1.0) * double(B) * Tn * C) * es);
+  grad_args(&a, p, out0, out1, gout, F, knots, c);
+  hipStream_t st = static_cast<hipStream_t>(c.stream);
+  const bool natural = c.method == kMethodNatural;
+  const double outs = natural ? 2.0 : 1.0;  // dense outputs written
+  ProfScope prof(XDE_KID_DENSE, (double(c.B) * c.H * c.C + double(c.B) * c.H + outs * double(c.B) * c.Tn * c.C) * elem_size(c.dtype));
   dim3 g(static_cast<unsigned>(p.blocks)), blk(kBlock);
-#define GRAD_DISPATCH(TY)                                                                            \
-  do {                                                                                               \
-    if (nat) {                                                                                       \
-      if (p.vec) XDE_LAUNCH((xde_cde_control_grad_kernel<TY, true, true>), g, blk, st, prof, a);     \
-      else XDE_LAUNCH((xde_cde_control_grad_kernel<TY, false, true>), g, blk, st, prof, a);          \
-    } else {                                                                                         \
-      if (p.vec) XDE_LAUNCH((xde_cde_control_grad_kernel<TY, true, false>), g, blk, st, prof, a);    \
-      else XDE_LAUNCH((xde_cde_control_grad_kernel<TY, false, false>), g, blk, st, prof, a);         \
-    }                                                                                                \
-  } while (0)
-  if (dtype == XDE_F32) GRAD_DISPATCH(float);
-  else GRAD_DISPATCH(double);
-#undef GRAD_DISPATCH
+  with_dtype(c.dtype, [&](auto ty) {
+    using T = typename decltype(ty)::type;
+    with_flag(natural, [&](auto nat) {
+      with_flag(p.vec != 0, [&](auto vec) {
+        XDE_LAUNCH((xde_cde_control_grad_kernel<T, decltype(vec)::value, decltype(nat)::value>), g, blk, st, prof, a);
+      });
+    });
+  });
   HIP_TRY(hipGetLastError());
   return XDE_OK;
 }
@@ -425,85 +401,63 @@ extern "C" {
 
 int xde_cde_control_grad(void* gSeries, const void* gout, const void* F, const void* knots, const void* t_dev, double t_host,
                          int time_dtype, int64_t B, int H, int C, int Tn, int method, int dtype, void* stream) {
-  if (method == kGradNatural) return fail(XDE_EBADARG, "xde_cde_control_grad: unknown method");
-  return grad_launch("xde_cde_control_grad", gSeries, nullptr, gout, F, knots, t_dev, t_host, time_dtype, B, H, C, Tn, method, dtype,
-                     stream);
+  const TimedCall c{t_dev, t_host, time_dtype, B, H, C, Tn, method, dtype, stream};
+  if (int rc = check_timed(ArgCheck{"xde_cde_control_grad"}.public_method(method), {gSeries, gout, F, knots}, c)) return rc;
+  return grad_launch(gSeries, nullptr, gout, F, knots, c);
 }
 
 int xde_cde_control_grad_natural(void* gY, void* gM, const void* gout, const void* F, const void* knots, const void* t_dev, double t_host,
                                  int time_dtype, int64_t B, int H, int C, int Tn, int dtype, void* stream) {
-  return grad_launch("xde_cde_control_grad_natural", gY, gM, gout, F, knots, t_dev, t_host, time_dtype, B, H, C, Tn, kGradNatural, dtype,
-                     stream);
+  const TimedCall c{t_dev, t_host, time_dtype, B, H, C, Tn, kMethodNatural, dtype, stream};
+  if (int rc = check_timed({"xde_cde_control_grad_natural"}, {gY, gM, gout, F, knots}, c)) return rc;
+  return grad_launch(gY, gM, gout, F, knots, c);
 }
 
 int xde_cde_control_grad_plan(const void* F, int64_t B, int H, int C, int dtype, xde_cdegrad_plan_t* plan) {
-  const std::string who = "xde_cde_control_grad_plan";
-  if (!plan) return fail(XDE_EBADARG, who + ": null pointer");
-  if (B < 1 || H < 1 || C < 1) return fail(XDE_EBADARG, who + ": bad sizes (need B, H, C >= 1)");
-  if (dtype != XDE_F32 && dtype != XDE_F64) return fail(XDE_EBADARG, who + ": bad dtype");
-  if (misaligned(F, dtype)) return fail(XDE_EBADARG, who + ": operand not aligned to its element type");
+  const int rc = ArgCheck{"xde_cde_control_grad_plan"}.not_null({plan}).sizes("B, H, C", {B, H, C}).dtype(dtype).aligned({F}, dtype).rc;
+  if (rc) return rc;
   *plan = grad_plan(F, B, H, C, dtype);
   return XDE_OK;
 }
 
 int64_t xde_spline_natural_coeffs_backward_workspace_bytes(int64_t B, int Tn, int C, int dtype) {
   if (B < 1 || C < 1 || Tn < 2 || (dtype != XDE_F32 && dtype != XDE_F64)) return -1;
-  return 2 * B * int64_t(Tn) * C * (dtype == XDE_F32 ? 4 : 8);
+  return 2 * B * int64_t(Tn) * C * elem_size(dtype);
 }
 
 int xde_spline_natural_coeffs_backward(void* gSeries, const void* gY, const void* gM, const void* series, const void* knots,
                                        void* workspace, int64_t B, int Tn, int C, int dtype, void* stream) {
-  const std::string who = "xde_spline_natural_coeffs_backward";
-  if (!gSeries || !gY || !gM || !series || !knots || !workspace) return fail(XDE_EBADARG, who + ": null pointer");
-  if (B < 1 || C < 1) return fail(XDE_EBADARG, who + ": bad sizes (need B, C >= 1)");
-  if (Tn < 2) return fail(XDE_EBADARG, who + ": bad sizes (need Tn >= 2)");
-  if (dtype != XDE_F32 && dtype != XDE_F64) return fail(XDE_EBADARG, who + ": bad dtype");
-  const void* ps[6] = {gSeries, gY, gM, series, knots, workspace};
-  for (const void* p : ps)
-    if (misaligned(p, dtype)) return fail(XDE_EBADARG, who + ": operand not aligned to its element type");
+  const Ptrs operands = {gSeries, gY, gM, series, knots, workspace};
+  if (int rc = check_rows({"xde_spline_natural_coeffs_backward"}, operands, {}, "B, C", {B, C}, Tn, dtype)) return rc;
   const int64_t cols = B * int64_t(C), n = cols * Tn;
-  int64_t blocks = (cols + kBlock - 1) / kBlock;
-  if (blocks > grid_cap()) blocks = grid_cap();
   hipStream_t st = static_cast<hipStream_t>(stream);
-  ProfScope prof(XDE_KID_DENSE, 8.0 * double(n) * (dtype == XDE_F32 ? 4.0 : 8.0));
-  dim3 g(static_cast<unsigned>(blocks)), blk(kBlock);
-  if (dtype == XDE_F32)
-    XDE_LAUNCH((xde_natural_coeffs_backward_kernel<float>), g, blk, st, prof, static_cast<float*>(gSeries), static_cast<const float*>(gY),
-               static_cast<const float*>(gM), static_cast<const float*>(series), static_cast<const float*>(knots),
-               static_cast<float*>(workspace), static_cast<float*>(workspace) + n, cols, Tn, C);
-  else
-    XDE_LAUNCH((xde_natural_coeffs_backward_kernel<double>), g, blk, st, prof, static_cast<double*>(gSeries),
-               static_cast<const double*>(gY), static_cast<const double*>(gM), static_cast<const double*>(series),
-               static_cast<const double*>(knots), static_cast<double*>(workspace), static_cast<double*>(workspace) + n, cols, Tn, C);
+  ProfScope prof(XDE_KID_DENSE, 8.0 * double(n) * elem_size(dtype));
+  dim3 g(grid_for(cols)), blk(kBlock);
+  with_dtype(dtype, [&](auto ty) {
+    using T = typename decltype(ty)::type;
+    XDE_LAUNCH((xde_natural_coeffs_backward_kernel<T>), g, blk, st, prof, static_cast<T*>(gSeries), static_cast<const T*>(gY),
+               static_cast<const T*>(gM), static_cast<const T*>(series), static_cast<const T*>(knots), static_cast<T*>(workspace),
+               static_cast<T*>(workspace) + n, cols, Tn, C);
+  });
   HIP_TRY(hipGetLastError());
   return XDE_OK;
 }
 
 int xde_spline_natural_gather_backward(void* gY, void* gM, const void* gval, const void* gder, const void* knots, const void* tq,
                                        int64_t outer, int Tn, int L, int D, int dtype, void* stream) {
-  const std::string who = "xde_spline_natural_gather_backward";
-  if (!gY || !gM || !knots || !tq || (!gval && !gder)) return fail(XDE_EBADARG, who + ": null pointer");
-  if (outer < 1 || L < 1 || D < 1) return fail(XDE_EBADARG, who + ": bad sizes (need outer, L, D >= 1)");
-  if (Tn < 2) return fail(XDE_EBADARG, who + ": bad sizes (need Tn >= 2)");
-  if (dtype != XDE_F32 && dtype != XDE_F64) return fail(XDE_EBADARG, who + ": bad dtype");
-  const void* ps[6] = {gY, gM, gval, gder, knots, tq};
-  for (const void* p : ps)
-    if (misaligned(p, dtype)) return fail(XDE_EBADARG, who + ": operand not aligned to its element type");
+  const ArgCheck no = ArgCheck{"xde_spline_natural_gather_backward"}.either(gval, gder);
+  if (int rc = check_rows(no, {gY, gM, knots, tq}, {gval, gder}, "outer, L, D", {outer, L, D}, Tn, dtype)) return rc;
   const int64_t cols = outer * int64_t(D);
-  int64_t blocks = (cols + kBlock - 1) / kBlock;
-  if (blocks > grid_cap()) blocks = grid_cap();
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const double es = dtype == XDE_F32 ? 4.0 : 8.0;
-  ProfScope prof(XDE_KID_DENSE, (2.0 * double(cols) * Tn + ((gval ? 1.0 : 0.0) + (gder ? 1.0 : 0.0)) * double(cols) * L) * es);
-  dim3 g(static_cast<unsigned>(blocks)), blk(kBlock);
-  if (dtype == XDE_F32)
-    XDE_LAUNCH((xde_natural_gather_backward_kernel<float>), g, blk, st, prof, static_cast<float*>(gY), static_cast<float*>(gM),
-               static_cast<const float*>(gval), static_cast<const float*>(gder), static_cast<const float*>(knots),
-               static_cast<const float*>(tq), cols, Tn, D, L);
-  else
-    XDE_LAUNCH((xde_natural_gather_backward_kernel<double>), g, blk, st, prof, static_cast<double*>(gY), static_cast<double*>(gM),
-               static_cast<const double*>(gval), static_cast<const double*>(gder), static_cast<const double*>(knots),
-               static_cast<const double*>(tq), cols, Tn, D, L);
+  const double cotangents = (gval ? 1.0 : 0.0) + (gder ? 1.0 : 0.0);
+  ProfScope prof(XDE_KID_DENSE, (2.0 * double(cols) * Tn + cotangents * double(cols) * L) * elem_size(dtype));
+  dim3 g(grid_for(cols)), blk(kBlock);
+  with_dtype(dtype, [&](auto ty) {
+    using T = typename decltype(ty)::type;
+    XDE_LAUNCH((xde_natural_gather_backward_kernel<T>), g, blk, st, prof, static_cast<T*>(gY), static_cast<T*>(gM),
+               static_cast<const T*>(gval), static_cast<const T*>(gder), static_cast<const T*>(knots), static_cast<const T*>(tq), cols,
+               Tn, D, L);
+  });
   HIP_TRY(hipGetLastError());
   return XDE_OK;
 }

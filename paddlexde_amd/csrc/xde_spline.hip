@@ -11,6 +11,7 @@
 #include "xde_hip_spline.h"
 
 #include "xde_common.hpp"
+#include "xde_control_host.hpp"
 #include "xde_spline_device.hpp"
 
 using namespace xde;
@@ -135,74 +136,47 @@ __global__ __launch_bounds__(kBlock) void xde_natural_gather_kernel(T* __restric
   }
 }
 
-bool misaligned(const void* p, int dtype) { return (reinterpret_cast<uintptr_t>(p) & (dtype == XDE_F32 ? 3u : 7u)) != 0; }
-
 }  // namespace
 
 extern "C" {
 
 int xde_spline_natural_coeffs(void* Y, void* M, const void* series, const void* knots, int64_t B, int Tn, int C, int dtype, void* stream) {
-  const std::string who = "xde_spline_natural_coeffs";
-  if (!Y || !M || !series || !knots) return fail(XDE_EBADARG, who + ": null pointer");
-  if (B < 1 || C < 1) return fail(XDE_EBADARG, who + ": bad sizes (need B, C >= 1)");
-  if (Tn < 2) return fail(XDE_EBADARG, who + ": bad sizes (need Tn >= 2)");
-  if (dtype != XDE_F32 && dtype != XDE_F64) return fail(XDE_EBADARG, who + ": bad dtype");
-  const void* ps[4] = {Y, M, series, knots};
-  for (const void* p : ps)
-    if (misaligned(p, dtype)) return fail(XDE_EBADARG, who + ": operand not aligned to its element type");
+  if (int rc = check_rows({"xde_spline_natural_coeffs"}, {Y, M, series, knots}, {}, "B, C", {B, C}, Tn, dtype)) return rc;
   const int64_t cols = B * int64_t(C);
-  int64_t blocks = (cols + kBlock - 1) / kBlock;
-  if (blocks > grid_cap()) blocks = grid_cap();
   hipStream_t st = static_cast<hipStream_t>(stream);
-  ProfScope prof(XDE_KID_DENSE, 3.0 * double(cols) * Tn * (dtype == XDE_F32 ? 4.0 : 8.0));
-  dim3 g(static_cast<unsigned>(blocks)), blk(kBlock);
-  if (dtype == XDE_F32)
-    XDE_LAUNCH((xde_natural_coeffs_kernel<float>), g, blk, st, prof, static_cast<float*>(Y), static_cast<float*>(M),
-               static_cast<const float*>(series), static_cast<const float*>(knots), cols, Tn, C);
-  else
-    XDE_LAUNCH((xde_natural_coeffs_kernel<double>), g, blk, st, prof, static_cast<double*>(Y), static_cast<double*>(M),
-               static_cast<const double*>(series), static_cast<const double*>(knots), cols, Tn, C);
+  ProfScope prof(XDE_KID_DENSE, 3.0 * double(cols) * Tn * elem_size(dtype));
+  dim3 g(grid_for(cols)), blk(kBlock);
+  with_dtype(dtype, [&](auto ty) {
+    using T = typename decltype(ty)::type;
+    XDE_LAUNCH((xde_natural_coeffs_kernel<T>), g, blk, st, prof, static_cast<T*>(Y), static_cast<T*>(M), static_cast<const T*>(series),
+               static_cast<const T*>(knots), cols, Tn, C);
+  });
   HIP_TRY(hipGetLastError());
   return XDE_OK;
 }
 
 int xde_spline_natural_gather(void* val, void* der, const void* Y, const void* M, const void* knots, const void* tq, int64_t outer, int Tn,
                               int L, int D, int dtype, void* stream) {
-  const std::string who = "xde_spline_natural_gather";
-  if (!val || !Y || !M || !knots || !tq) return fail(XDE_EBADARG, who + ": null pointer");
-  if (outer < 1 || L < 1 || D < 1) return fail(XDE_EBADARG, who + ": bad sizes (need outer, L, D >= 1)");
-  if (Tn < 2) return fail(XDE_EBADARG, who + ": bad sizes (need Tn >= 2)");
-  if (dtype != XDE_F32 && dtype != XDE_F64) return fail(XDE_EBADARG, who + ": bad dtype");
-  const void* ps[6] = {val, der, Y, M, knots, tq};
-  for (const void* p : ps)
-    if (misaligned(p, dtype)) return fail(XDE_EBADARG, who + ": operand not aligned to its element type");
-  const int width = dtype == XDE_F32 ? 4 : 2;
+  // (`der` may be null)
+  if (int rc = check_rows({"xde_spline_natural_gather"}, {val, Y, M, knots, tq}, {der}, "outer, L, D", {outer, L, D}, Tn, dtype))
+    return rc;
+  const int width = vec_width(dtype);
   const bool vec = (D % width) == 0 && aligned16(val) && aligned16(der) && aligned16(Y) && aligned16(M);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const double es = dtype == XDE_F32 ? 4.0 : 8.0;
-#define LAUNCH_NG(TY)                                                                                                                \
-  do {                                                                                                                               \
-    if (vec)                                                                                                                         \
-      XDE_LAUNCH((xde_natural_gather_kernel<TY, true>), g, b, st, prof, static_cast<TY*>(val), static_cast<TY*>(der),                 \
-                 static_cast<const TY*>(Y), static_cast<const TY*>(M), static_cast<const TY*>(knots), static_cast<const TY*>(tq), outer, \
-                 Tn, D, L, l0, Lt);                                                                                                  \
-    else                                                                                                                             \
-      XDE_LAUNCH((xde_natural_gather_kernel<TY, false>), g, b, st, prof, static_cast<TY*>(val), static_cast<TY*>(der),                \
-                 static_cast<const TY*>(Y), static_cast<const TY*>(M), static_cast<const TY*>(knots), static_cast<const TY*>(tq), outer, \
-                 Tn, D, L, l0, Lt);                                                                                                  \
-  } while (0)
   for (int l0 = 0; l0 < L; l0 += kNatMaxL) {
     const int Lt = L - l0 < kNatMaxL ? L - l0 : kNatMaxL;
-    const int64_t work = outer * int64_t(Lt) * (vec ? D / width : D);
-    int64_t blocks = (work + kBlock - 1) / kBlock;
-    if (blocks > grid_cap()) blocks = grid_cap();
-    ProfScope prof(XDE_KID_DENSE, (der ? 6.0 : 5.0) * double(outer) * Lt * D * es);
-    dim3 g(static_cast<unsigned>(blocks)), b(kBlock);
-    if (dtype == XDE_F32) LAUNCH_NG(float);
-    else LAUNCH_NG(double);
+    ProfScope prof(XDE_KID_DENSE, (der ? 6.0 : 5.0) * double(outer) * Lt * D * elem_size(dtype));
+    dim3 g(grid_for(outer * int64_t(Lt) * (vec ? D / width : D))), b(kBlock);
+    with_dtype(dtype, [&](auto ty) {
+      using T = typename decltype(ty)::type;
+      with_flag(vec, [&](auto v) {
+        XDE_LAUNCH((xde_natural_gather_kernel<T, decltype(v)::value>), g, b, st, prof, static_cast<T*>(val), static_cast<T*>(der),
+                   static_cast<const T*>(Y), static_cast<const T*>(M), static_cast<const T*>(knots), static_cast<const T*>(tq), outer, Tn,
+                   D, L, l0, Lt);
+      });
+    });
     HIP_TRY(hipGetLastError());
   }
-#undef LAUNCH_NG
   return XDE_OK;
 }
 

@@ -10,6 +10,12 @@
 
 namespace xde {
 
+// the time of a launch that takes one: the float64 (`time_f64`) or float32 element `t_dev` points at, else the host's number
+__device__ __forceinline__ double launch_time(const void* t_dev, int time_f64, double t_host) {
+  if (!t_dev) return t_host;
+  return time_f64 ? *static_cast<const double*>(t_dev) : double(*static_cast<const float*>(t_dev));
+}
+
 // ------------------------------------------------------------------------------------------
 // "weighted rows": LinearInterpolation (M = 2) and BezierSpline (M = 4)
 // ------------------------------------------------------------------------------------------

@@ -19,6 +19,14 @@ from .. import _hip
 __all__ = ["LinearInterpolation", "CubicHermiteSpline", "BezierSpline", "NaturalCubicSpline"]
 
 
+def _gather_buffers(rows, t):
+    """What a gather of rows ``[..., T, D]`` at the times ``t`` takes: the query times ``tq [L]`` (detached, contiguous, in the rows'
+    dtype on their device) and the empty outputs ``val, der [..., L, D]``."""
+    tq = torch.as_tensor(t).detach().to(device=rows.device, dtype=rows.dtype).contiguous().reshape(-1)
+    val = torch.empty(tuple(rows.shape[:-2]) + (tq.numel(), rows.shape[-1]), dtype=rows.dtype, device=rows.device)
+    return tq, val, torch.empty_like(val)
+
+
 class InterpolationBase:
     method = None  # "linear" | "cubic" | "bez": the kernels' name of the spline
     min_times = 2
@@ -60,10 +68,7 @@ class InterpolationBase:
                 "{}(differentiable=True): evaluate / derivative are not differentiable; the values at the knots are the series rows "
                 "themselves (index the series, e.g. series[..., 0, :] for z0), and cdeint differentiates X'(t) inside its "
                 "contraction; NaturalCubicSpline(differentiable=True) has differentiable evaluate / derivative".format(type(self).__name__))
-        tq = torch.as_tensor(t).detach().to(device=self._series.device, dtype=self._series.dtype).contiguous().reshape(-1)
-        shape = tuple(self._series.shape[:-2]) + (tq.numel(), self._series.shape[-1])
-        val = torch.empty(shape, dtype=self._series.dtype, device=self._series.device)
-        der = torch.empty_like(val)
+        tq, val, der = _gather_buffers(self._series, t)
         self._backend.history_gather(val, der, self._series, self._t, tq, self.method)
         return val, der
 
@@ -129,10 +134,8 @@ class _NaturalGatherFn(torch.autograd.Function):
     xde_spline_natural_gather_backward launch ((c) of the same header) over whichever of the two cotangents arrived."""
 
     @staticmethod
-    def forward(ctx, Y, M, knots, tq):
-        shape = tuple(Y.shape[:-2]) + (tq.numel(), Y.shape[-1])
-        val = torch.empty(shape, dtype=Y.dtype, device=Y.device)
-        der = torch.empty_like(val)
+    def forward(ctx, Y, M, knots, t):
+        tq, val, der = _gather_buffers(Y, t)
         _hip.get_backend()._spline_natural_gather(val, der, Y, M, knots, tq)
         ctx.save_for_backward(knots, tq)
         ctx.shape = tuple(Y.shape)
@@ -192,11 +195,8 @@ class NaturalCubicSpline(InterpolationBase):
         self._coef = M.reshape(raw.shape)
 
     def _gather(self, t):
-        tq = torch.as_tensor(t).detach().to(device=self._series.device, dtype=self._series.dtype).contiguous().reshape(-1)
         if self.differentiable:
-            return _NaturalGatherFn.apply(self._series, self._coef, self._t, tq)
-        shape = tuple(self._series.shape[:-2]) + (tq.numel(), self._series.shape[-1])
-        val = torch.empty(shape, dtype=self._series.dtype, device=self._series.device)
-        der = torch.empty_like(val)
+            return _NaturalGatherFn.apply(self._series, self._coef, self._t, torch.as_tensor(t).detach())
+        tq, val, der = _gather_buffers(self._series, t)
         self._backend._spline_natural_gather(val, der, self._series, self._coef, self._t, tq)
         return val, der

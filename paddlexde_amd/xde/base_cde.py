@@ -26,37 +26,59 @@ from .base_ode import BaseODE
 __all__ = ["BaseCDE", "CDEField", "CdeContractFn", "CdeControlContractFn"]
 
 
+# The natural control has entry points of its own (its rows are ``Y`` and ``M``); every other control names its method.  Each kind of
+# launch makes that choice in one place: the contraction in the nodes' one forward, its cotangent in ``_launch_contract_backward``, the
+# control's cotangent in ``CdeControlContractFn.backward``.
+def _contract_forward(ctx, F, series, knots, t, method, coef, keep_F):
+    """The forward of both nodes: the launch, and what the backward needs — the control's tensors, ``t`` (saved when it is a tensor),
+    ``F``'s shape, and ``F`` itself only with ``keep_F`` (the node that differentiates the control)."""
+    be = _hip.get_backend()
+    F = F.contiguous()
+    out = torch.empty(F.shape[:2], dtype=F.dtype, device=F.device)  # (torch's allocator: capture-safe)
+    if method == "natural":
+        be._cde_contract_natural(out, F, series, coef, knots, t)
+    else:
+        be._cde_contract(out, F, series, knots, t, method)
+    ctx.method, ctx.t_host = method, None if torch.is_tensor(t) else t
+    ctx.f_shape = F.shape
+    ctx.save_for_backward(series, knots, *([coef] if method == "natural" else []), *([t] if torch.is_tensor(t) else []),
+                          *([F] if keep_F else []))
+    return out
+
+
+def _contract_saved(ctx):
+    """``series, coef, knots, t, F`` as the forward left them (``coef`` and ``F`` None where they were not saved)."""
+    series, knots, *rest = ctx.saved_tensors
+    coef = rest.pop(0) if ctx.method == "natural" else None
+    t = rest.pop(0) if ctx.t_host is None else ctx.t_host
+    return series, coef, knots, t, rest[0] if rest else None
+
+
+def _launch_contract_backward(gF, gout, series, coef, knots, t, method):
+    be = _hip.get_backend()
+    if method == "natural":
+        be._cde_contract_natural_backward(gF, gout, series, coef, knots, t)
+    else:
+        be._cde_contract_backward(gF, gout, series, knots, t, method)
+
+
 class CdeContractFn(torch.autograd.Function):
     """``out[b, h] = sum_c F[b, h, c] * X'(t)[b, c]`` for contiguous ``F [B, H, C]``, ``series [B, Tn, C]``, ``knots [Tn]`` and ``t`` a
     one-element device tensor (read by the kernel: no synchronisation, so a captured call replays with the element's current value) or
     a Python number.  With ``method`` "natural", ``series`` is the spline's ``Y`` and ``coef [B, Tn, C]`` its second derivatives ``M``.
-    Gradient to ``F`` only — the contraction is linear in it; the series, the coefficients, the knots and ``t`` get none."""
+    Gradient to ``F`` only — the contraction is linear in it, so ``F`` is not kept; the series, the coefficients, the knots and ``t``
+    get none."""
 
     @staticmethod
     def forward(ctx, F, series, knots, t, method, coef=None):
-        be = _hip.get_backend()
-        F = F.contiguous()
-        out = torch.empty(F.shape[:2], dtype=F.dtype, device=F.device)  # (torch's allocator: capture-safe)
-        if method == "natural":
-            be._cde_contract_natural(out, F, series, coef, knots, t)
-        else:
-            be._cde_contract(out, F, series, knots, t, method)
-        ctx.method, ctx.t_host = method, None if torch.is_tensor(t) else t
-        ctx.save_for_backward(series, knots, *([coef] if method == "natural" else []), *([t] if torch.is_tensor(t) else []))
-        ctx.f_shape = F.shape
-        return out
+        return _contract_forward(ctx, F, series, knots, t, method, coef, False)
 
     @staticmethod
     def backward(ctx, gout):
-        series, knots, *rest = ctx.saved_tensors
-        coef = rest.pop(0) if ctx.method == "natural" else None
-        t = rest[0] if rest else ctx.t_host
+        series, coef, knots, t, _ = _contract_saved(ctx)
         gout = gout.contiguous()
         gF = torch.empty(ctx.f_shape, dtype=gout.dtype, device=gout.device)
-        if coef is not None:
-            _hip.get_backend()._cde_contract_natural_backward(gF, gout, series, coef, knots, t)
-        else:
-            _hip.get_backend()._cde_contract_backward(gF, gout, series, knots, t, ctx.method)
+        _launch_contract_backward(gF, gout, series, coef, knots, t, ctx.method)
         return gF, None, None, None, None, None
 
 
@@ -68,39 +90,24 @@ class CdeControlContractFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, F, series, knots, t, method, coef=None):
-        be = _hip.get_backend()
-        F = F.contiguous()
-        out = torch.empty(F.shape[:2], dtype=F.dtype, device=F.device)
-        if method == "natural":
-            be._cde_contract_natural(out, F, series, coef, knots, t)
-        else:
-            be._cde_contract(out, F, series, knots, t, method)
-        ctx.method, ctx.t_host = method, None if torch.is_tensor(t) else t
-        ctx.save_for_backward(F, series, knots, *([coef] if method == "natural" else []), *([t] if torch.is_tensor(t) else []))
-        return out
+        return _contract_forward(ctx, F, series, knots, t, method, coef, True)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gout):
-        F, series, knots, *rest = ctx.saved_tensors
-        coef = rest.pop(0) if ctx.method == "natural" else None
-        t = rest[0] if rest else ctx.t_host
-        be = _hip.get_backend()
+        series, coef, knots, t, F = _contract_saved(ctx)
         gout = gout.contiguous()
         gF = g_series = g_coef = None
         if ctx.needs_input_grad[0]:
             gF = torch.empty_like(F)
-            if coef is not None:
-                be._cde_contract_natural_backward(gF, gout, series, coef, knots, t)
-            else:
-                be._cde_contract_backward(gF, gout, series, knots, t, ctx.method)
+            _launch_contract_backward(gF, gout, series, coef, knots, t, ctx.method)
         if ctx.needs_input_grad[1] or (coef is not None and ctx.needs_input_grad[5]):
             g_series = torch.empty_like(series)  # (every element is written by the launch: no memset)
             if coef is not None:
                 g_coef = torch.empty_like(coef)
-                be._cde_control_grad_natural(g_series, g_coef, gout, F, knots, t)
+                _hip.get_backend()._cde_control_grad_natural(g_series, g_coef, gout, F, knots, t)
             else:
-                be._cde_control_grad(g_series, gout, F, knots, t, ctx.method)
+                _hip.get_backend()._cde_control_grad(g_series, gout, F, knots, t, ctx.method)
         return gF, g_series, None, None, None, g_coef
 
 

@@ -134,6 +134,38 @@ def test_more_work_items_than_the_grid(dtype):
         assert {"kernel:scalar-grouped", "second-item:grouped", "second-pass:backward"} <= bwd, bwd
 
 
+@pytest.mark.parametrize("C", [5, 8])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
+def test_the_three_forms_of_time_give_the_same_bits(dtype, C):
+    """One shape and one time under all three forms of time (the other tests rotate the forms over their shapes): B, H, Tn = 2, 3, 4
+    on the unit grid, C = 5 (the scalar tail) and C = 8 (the vector path), at 1.375 (inside an interval, exact in float32) and 2.0 (on
+    a knot).  Both launches give identical bits whether the time is a float64 device element, an element of the series dtype or a
+    Python number, and they are the double's."""
+    be, double, T, th = _hip.get_backend(), CdeDoubleBackend(), _NPT[dtype], torch.from_numpy
+    B, H, Tn = 2, 3, 4
+    rs = np.random.RandomState(40 + C)
+    series, F, gout = rs.randn(B, Tn, C).astype(T), rs.randn(B, H, C).astype(T), rs.randn(B, H).astype(T)
+    knots = np.arange(Tn).astype(T)
+    ser_d, kn_d, F_d, gout_d = (_placed(x, False) for x in (series, knots, F, gout))
+    assert be._cde_plan(False, F_d, B, H, C)["vec"] == be._cde_plan(True, F_d, B, H, C)["vec"] == int(C == 8)
+    for method in ("linear", "cubic"):
+        for tv in (1.375, 2.0):
+            got = []
+            for form in range(3):
+                cpu_t = [torch.tensor(tv, dtype=torch.float64), torch.tensor([tv], dtype=dtype), tv][form]
+                want, gwant = torch.empty(B, H, dtype=dtype), torch.empty(B, H, C, dtype=dtype)
+                double._cde_contract(want, th(F), th(series), th(knots), cpu_t, method)
+                double._cde_contract_backward(gwant, th(gout), th(series), th(knots), cpu_t, method)
+                out, gF = _placed(np.full((B, H), SENTINEL, dtype=T), False), _placed(np.full((B, H, C), SENTINEL, dtype=T), False)
+                td = _time_forms(tv, dtype)[form]
+                be._cde_contract(out, F_d, ser_d, kn_d, td, method)
+                be._cde_contract_backward(gF, gout_d, ser_d, kn_d, td, method)
+                got.append((out.cpu().numpy(), gF.cpu().numpy()))
+                where = (dtype, method, C, tv, form)
+                assert np.array_equal(got[-1][0], want.numpy()) and np.array_equal(got[-1][1], gwant.numpy()), where
+                assert np.array_equal(got[-1][0], got[0][0]) and np.array_equal(got[-1][1], got[0][1]), where
+
+
 @pytest.mark.parametrize("row", P.TABLE, ids=P.ROW_IDS)
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
 def test_every_launch_plan_equals_the_double_bit_for_bit(dtype, row):

@@ -195,6 +195,38 @@ def test_the_natural_kernels_equal_the_double_bit_for_bit(dtype):
     assert double.launches.count("cde_contract_natural") == double.launches.count("cde_contract_natural_backward") == n
 
 
+@pytest.mark.parametrize("C", [5, 8])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
+def test_the_three_forms_of_time_give_the_same_bits_on_the_natural_control(dtype, C):
+    """One shape and one time under all three forms of time (the test above rotates the forms over its shapes): B, H, Tn = 2, 3, 4 on
+    the unit grid, C = 5 (the scalar tail) and C = 8 (the vector path), at 1.375 (inside an interval, exact in float32) and 2.0 (on a
+    knot).  Both natural launches give identical bits whether the time is a float64 device element, an element of the series dtype or a
+    Python number, and they are the double's."""
+    be, double, T = _hip.get_backend(), SD.SplineDoubleBackend(), _NPT[dtype]
+    B, H, Tn = 2, 3, 4
+    rs = np.random.RandomState(40 + C)
+    kn = np.arange(Tn).astype(T)
+    Y, M = SD.natural_coeffs(rs.randn(B, Tn, C).astype(T), kn)
+    F, gout = rs.randn(B, H, C).astype(T), rs.randn(B, H).astype(T)
+    Y_d, M_d, kn_d, F_d, gout_d = (_placed(x) for x in (Y, M, kn, F, gout))
+    assert be._cde_plan(False, F_d, B, H, C)["vec"] == be._cde_plan(True, F_d, B, H, C)["vec"] == int(C == 8)
+    for tv in (1.375, 2.0):
+        got = []
+        for form in range(3):
+            cpu_t = [torch.tensor(tv, dtype=torch.float64), torch.tensor([tv], dtype=dtype), tv][form]
+            want, gwant = torch.empty(B, H, dtype=dtype), torch.empty(B, H, C, dtype=dtype)
+            double._cde_contract_natural(want, th(F), th(Y), th(M), th(kn), cpu_t)
+            double._cde_contract_natural_backward(gwant, th(gout), th(Y), th(M), th(kn), cpu_t)
+            out, gF = _placed(np.full((B, H), SENTINEL, dtype=T)), _placed(np.full((B, H, C), SENTINEL, dtype=T))
+            td = [torch.tensor(tv, dtype=torch.float64, device=DEV), torch.tensor([tv], dtype=dtype, device=DEV), tv][form]
+            be._cde_contract_natural(out, F_d, Y_d, M_d, kn_d, td)
+            be._cde_contract_natural_backward(gF, gout_d, Y_d, M_d, kn_d, td)
+            got.append((out.cpu().numpy(), gF.cpu().numpy()))
+            where = (dtype, C, tv, form)
+            assert np.array_equal(got[-1][0], want.numpy()) and np.array_equal(got[-1][1], gwant.numpy()), where
+            assert np.array_equal(got[-1][0], got[0][0]) and np.array_equal(got[-1][1], got[0][1]), where
+
+
 @pytest.mark.parametrize("row", P.TABLE, ids=P.ROW_IDS)
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
 def test_every_launch_plan_equals_the_double_bit_for_bit_on_the_natural_control(dtype, row):
