@@ -254,7 +254,14 @@ CDEGRAD_PROTOTYPES = {
     "xde_spline_natural_coeffs_backward_workspace_bytes": (_i64, [_i64, _i32, _i32, _i32]),
     "xde_spline_natural_gather_backward": (_i32, [_vp] * 6 + [_i64, _i32, _i32, _i32, _i32, _vp]),
 }
+# the entry points of include/xde_hip_kl.h (the KL term of a latent SDE fused into the Euler-Maruyama step, and its cotangents); bound by
+# load_library() after _bind_cdegrad
+KL_PROTOTYPES = {
+    "xde_sde_kl_step": (_i32, [_vp] * 7 + [_i64, _i64, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
+    "xde_sde_kl_backward": (_i32, [_vp] * 8 + [_i64, _i64, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
+}
 SYMBOLS = tuple(PROTOTYPES)
+KL_SYMBOLS = tuple(KL_PROTOTYPES)
 BACKPROP_SYMBOLS = tuple(BACKPROP_PROTOTYPES)
 GRID_SYMBOLS = tuple(GRID_PROTOTYPES)
 SDE_SYMBOLS = tuple(SDE_PROTOTYPES)
@@ -293,7 +300,7 @@ _REBUILD = "rebuild it with `python -m paddlexde_amd.csrc.build --force`"
 
 
 def _declare(lib, sym):
-    proto = PROTOTYPES.get(sym) or BACKPROP_PROTOTYPES.get(sym) or GRID_PROTOTYPES.get(sym) or SDE_PROTOTYPES.get(sym) or CDE_PROTOTYPES.get(sym) or SEAM_PROTOTYPES.get(sym) or SPLINE_PROTOTYPES.get(sym) or CDEGRAD_PROTOTYPES[sym]
+    proto = PROTOTYPES.get(sym) or BACKPROP_PROTOTYPES.get(sym) or GRID_PROTOTYPES.get(sym) or SDE_PROTOTYPES.get(sym) or CDE_PROTOTYPES.get(sym) or SEAM_PROTOTYPES.get(sym) or SPLINE_PROTOTYPES.get(sym) or CDEGRAD_PROTOTYPES.get(sym) or KL_PROTOTYPES[sym]
     try:
         fn = getattr(lib, sym)
     except AttributeError:
@@ -357,6 +364,12 @@ def _bind_cdegrad(lib):
         _declare(lib, sym)
 
 
+def _bind_kl(lib):
+    """Declare the entry points of include/xde_hip_kl.h on ``lib`` (after ``_bind``: the ABI check comes first)."""
+    for sym in KL_SYMBOLS:
+        _declare(lib, sym)
+
+
 def load_library():
     """dlopen libxde_hip.so and declare prototypes.  Raises if it has not been built, or is not the library this binding speaks to."""
     global _lib
@@ -378,6 +391,7 @@ def load_library():
         _bind_seam(lib)
         _bind_spline(lib)
         _bind_cdegrad(lib)
+        _bind_kl(lib)
         _lib = lib
     return _lib
 
@@ -991,6 +1005,39 @@ class HipBackend:
             return
         rc = self.lib.xde_sde_noise(out.data_ptr(), out.numel(), int(seed), int(k), mode, dt, self._stream(out))
         self._check(rc, "xde_sde_noise")
+
+    # -- the KL term of a latent SDE fused into the Euler-Maruyama step (include/xde_hip_kl.h) ----------------------------------------
+    # Private for the reason _sde_em_step is.  Only the fixed-step solvers' logqp path (and its autograd nodes) call these.
+    def _kl_call(self, who, state, accs, like, *scalars):
+        """The operand check the two KL entry points share; nothing is launched here.  ``state`` must be contiguous device tensors of
+        ``like``'s shape and dtype and ``accs`` contiguous float64 device tensors with one element per row of ``like`` (a row is its
+        last axis); None stands for a null pointer and is not checked.  Returns ``(rows, D, tail)``, ``tail`` being ``scalars`` followed
+        by the dtype code and the stream: the arguments the caller's launch puts after its pointers."""
+        self._require_device(*state, *accs)
+        D = like.shape[-1]
+        rows = like.numel() // D if D else 0
+        for x in state:
+            if x is not None and (not x.is_contiguous() or x.shape != like.shape or x.dtype != like.dtype):
+                raise XdeError("{}: the state operands must be contiguous tensors of one shape and dtype".format(who))
+        for x in accs:
+            if x is not None and (not x.is_contiguous() or x.dtype != torch.float64 or x.numel() != rows):
+                raise XdeError("{}: an accumulator is a contiguous float64 tensor with one element per row".format(who))
+        return rows, D, scalars + (dtype_code(like.dtype), self._stream(like))
+
+    def _sde_kl_step(self, y1, acc1, y0, f, g, h, acc0, dt, s, seed, k):
+        """``y1 = (y0 + f*dt) + g*(s*Z)`` (xde_sde_em_step's bits) and, per row of the last axis, ``acc1 = acc0 + sum(((f - h)/g)**2) *
+        (0.5*dt)`` in float64 — one launch.  ``acc0`` None: zero; ``acc1`` may be ``acc0`` and ``y1`` may be ``y0``; ``y1`` and ``y0``
+        both None: only the accumulation (no generator)."""
+        rows, D, tail = self._kl_call("_sde_kl_step", (y1, y0, f, g, h), (acc1, acc0), f, float(dt), float(s), int(seed), int(k))
+        rc = self.lib.xde_sde_kl_step(_ptr(y1), _ptr(acc1), _ptr(y0), _ptr(f), _ptr(g), _ptr(h), _ptr(acc0), rows, D, *tail)
+        self._check(rc, "xde_sde_kl_step")
+
+    def _sde_kl_backward(self, gf, gg, gh, gy1, gacc, f, g, h, dt, s, seed, k):
+        """The cotangents of ``f``, ``g`` and ``h`` (any may be None: skipped) from those of ``y1`` (``gy1``; None: the accumulate-only
+        mode's backward) and of ``acc1`` (``gacc``, float64 per row), one launch regenerating the forward's Z."""
+        rows, D, tail = self._kl_call("_sde_kl_backward", (gf, gg, gh, gy1, f, g, h), (gacc,), f, float(dt), float(s), int(seed), int(k))
+        rc = self.lib.xde_sde_kl_backward(_ptr(gf), _ptr(gg), _ptr(gh), _ptr(gy1), _ptr(gacc), _ptr(f), _ptr(g), _ptr(h), rows, D, *tail)
+        self._check(rc, "xde_sde_kl_backward")
 
     # -- the seam between two attempts as one resident launch (include/xde_hip_seam.h) ------------------------------------------------
     # Private for the reason _interp_rows is: the public methods are the contract tests/_cpu_double.py mirrors.  Only AdaptiveRKSolver

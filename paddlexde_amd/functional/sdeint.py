@@ -40,7 +40,14 @@ def sdeint(
     ``options["seed"]`` (an int, 0 <= seed < 2**64) fixes the Brownian path; without it the seed is drawn from torch's default CPU
     generator, so ``torch.manual_seed`` makes a run repeatable.  The other options are the fixed solvers' (``step_size`` /
     ``grid_constructor`` sub-stepping with ``interp="linear"``, ``pipeline`` "auto" or "sync").  ``reverse`` is accepted and has
-    no effect, as in the reference; a decreasing ``t`` integrates backwards with ``dW = sqrt(|dt|) * Z``."""
+    no effect, as in the reference; a decreasing ``t`` integrates backwards with ``dW = sqrt(|dt|) * Z``.
+
+    ``options={"logqp": True, "prior_drift": h}`` (a latent SDE; ``solver=Euler`` or ``Milstein``): returns ``(ys, logqp)``, ``ys`` the
+    same path bit for bit and ``logqp[..., i]`` — shape ``y0.shape[:-1] + (T - 1,)``, the state dtype — the KL divergence over
+    ``[t[i], t[i+1]]`` between the path's law and that of ``dy = h(t, y) dt + diffusion(t, y) dW``: the scheme's sum of
+    ``0.5 * |(drift - h) / diffusion|**2 * dt`` over the last axis, accumulated in float64 by the step launch itself
+    (include/xde_hip_kl.h).  ``h(t, y)`` returns a tensor of ``y``'s shape and dtype; ``diffusion`` must be non-zero.  Gradients reach
+    ``y0`` and the parameters of all three functions, from ``ys`` and from ``logqp``."""
     if isinstance(y0, (tuple, list)):
         raise NotImplementedError("sdeint takes a tensor y0, not a tuple: stack the members into one state tensor")
     if not (isinstance(solver, type) and issubclass(solver, FixedSolver)):
@@ -53,12 +60,24 @@ def sdeint(
                                   "of drift and diffusion)")
     options = dict(options)
     seed = options.pop("seed", None)
+    logqp = bool(options.pop("logqp", False))
+    prior = options.pop("prior_drift", None)
+    if logqp and prior is None:
+        raise ValueError("options['logqp'] needs the prior drift: options={'logqp': True, 'prior_drift': h} with h(t, y) a tensor of y's "
+                         "shape and dtype (the KL term is between dy = drift dt + diffusion dW and dy = h dt + diffusion dW)")
+    if prior is not None and not logqp:
+        raise ValueError("options['prior_drift'] is only read with options['logqp'] = True (sdeint then returns (ys, logqp)); drop it, "
+                         "or ask for logqp")
 
-    xde = BaseSDE(f=drift, g=diffusion, y0=y0, t_span=t, reverse=reverse, seed=seed)
+    xde = BaseSDE(f=drift, g=diffusion, y0=y0, t_span=t, reverse=reverse, seed=seed, prior=prior)
 
+    if logqp:
+        options["logqp"] = True  # (refused by the solvers whose step cannot accumulate it, before the first launch)
     s = solver(xde=xde, y0=xde.y0, rtol=rtol, atol=atol, **options)
     solution = s.integrate(t)
 
     solution = xde.format(solution)
 
+    if logqp:
+        return solution, s.logqp
     return solution

@@ -172,6 +172,11 @@ def sdeint_adjoint(
     ``diffusion``, which then must be ``nn.Module``s.  The backward is once-differentiable; there is no gradient with respect to ``t``.
     The sweep is the scheme's own, so ``adjoint_solver``, ``adjoint_rtol``, ``adjoint_atol``, ``adjoint_options`` and ``event_fn`` must
     be None."""
+    for key in ("logqp", "prior_drift"):
+        if key in dict(options):
+            raise NotImplementedError("sdeint_adjoint does not take options[{!r}]: the KL term of a latent SDE is accumulated by "
+                                      "sdeint(..., solver=Euler) or solver=Milstein, which keep the steps' operands for the "
+                                      "backward".format(key))
     if solver is not ReversibleHeun:
         raise NotImplementedError(_MESSAGE)
     for name, value in (("adjoint_solver", adjoint_solver), ("adjoint_rtol", adjoint_rtol), ("adjoint_atol", adjoint_atol),

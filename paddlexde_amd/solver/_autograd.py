@@ -1,4 +1,4 @@
-"""Autograd nodes around the step kernels (xde_stage_combine, xde_interp_rows, xde_sde_em_step, xde_sde_milstein_step, xde_sde_srk_*, xde_sde_rheun_*) for discretise-then-optimise training.
+"""Autograd nodes around the step kernels (xde_stage_combine, xde_interp_rows, xde_sde_em_step, xde_sde_milstein_step, xde_sde_srk_*, xde_sde_rheun_*, xde_sde_kl_*) for discretise-then-optimise training.
 
 The reference trains by back-propagating through its eager solver ops (example/ode_demo.py:51-53:
 ``pred_y = odeint(func, batch_y0, t_span, solver=RK4); loss.backward()``).  Here the forward is one combine launch
@@ -273,3 +273,68 @@ class SdeRheunCorrectFn(torch.autograd.Function):
         needs = ctx.needs_input_grad[5:10]
         g, gf, gg = _sde_backward(ctx.backend._sde_em_backward, g, (needs[0], needs[1] or needs[2], needs[3] or needs[4]), ctx.meta)
         return (None,) * 5 + (g, gf if needs[1] else None, gf if needs[2] else None, gg if needs[3] else None, gg if needs[4] else None)
+
+
+class SdeKlEulerFn(torch.autograd.Function):
+    """One Euler-Maruyama step fused with the KL accumulation of a latent SDE (``HipBackend._sde_kl_step``) as an autograd node with two
+    outputs: ``y1 = (y0 + f*dt) + g*(s*Z)`` and ``acc1 = acc0 + sum(((f - h)/g)**2, -1) * (0.5*dt)`` (float64 per row; ``acc0`` None:
+    zero).  The node saves ``f, g, h`` and ``(dt, s, seed, k)``; backward is one xde_sde_kl_backward launch that regenerates Z
+    (``gy0 = gy1`` and ``gacc0 = gacc1`` need none).  A cotangent that is absent stays absent: without ``gacc1`` the backward is
+    xde_sde_em_backward, without ``gy1`` the accumulate-only mode's."""
+
+    @staticmethod
+    def forward(ctx, backend, dt, s, seed, k, y0, f, g, h, acc0):
+        y1 = torch.empty_like(y0)
+        acc1 = torch.empty(y0.shape[:-1], dtype=torch.float64, device=y0.device)
+        backend._sde_kl_step(y1, acc1, y0.detach(), f.detach(), g.detach(), h.detach(), None if acc0 is None else acc0.detach(), dt, s,
+                             seed, k)
+        ctx.backend, ctx.meta = backend, (float(dt), float(s), int(seed), int(k))
+        ctx.save_for_backward(f, g, h)
+        ctx.set_materialize_grads(False)
+        return y1, acc1
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy1, gacc):
+        needs = ctx.needs_input_grad[5:10]
+        if gy1 is not None:
+            gy1 = _cotangent(gy1)
+        gf = gg = gh = None
+        if gacc is None:
+            if gy1 is not None:
+                _, gf, gg = _sde_backward(ctx.backend._sde_em_backward, gy1, (False,) + tuple(needs[1:3]), ctx.meta)
+        else:
+            gacc = gacc.contiguous()
+            f, g, h = ctx.saved_tensors
+            gf, gg, gh = (torch.empty_like(f) if need else None for need in needs[1:4])
+            if any(o is not None for o in (gf, gg, gh)):
+                ctx.backend._sde_kl_backward(gf, gg, gh, gy1, gacc, f, g, h, *ctx.meta)
+        return (None,) * 5 + (gy1 if needs[0] else None, gf, gg, gh, gacc if needs[4] else None)
+
+
+class SdeKlAccFn(torch.autograd.Function):
+    """The KL accumulation alone (``HipBackend._sde_kl_step`` in its accumulate-only mode: Milstein's step keeps its own launches) as an
+    autograd node: ``acc1 = acc0 + sum(((f - h)/g)**2, -1) * (0.5*dt)``.  The node saves ``f, g, h`` and ``dt``; backward is one
+    xde_sde_kl_backward launch without ``gy1`` (no generator); ``gacc0 = gacc1``."""
+
+    @staticmethod
+    def forward(ctx, backend, dt, f, g, h, acc0):
+        acc1 = torch.empty(f.shape[:-1], dtype=torch.float64, device=f.device)
+        backend._sde_kl_step(None, acc1, None, f.detach(), g.detach(), h.detach(), None if acc0 is None else acc0.detach(), dt, 0.0, 0, 0)
+        ctx.backend, ctx.dt = backend, float(dt)
+        ctx.save_for_backward(f, g, h)
+        ctx.set_materialize_grads(False)
+        return acc1
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gacc):
+        if gacc is None:
+            return (None,) * 6
+        needs = ctx.needs_input_grad[2:6]
+        gacc = gacc.contiguous()
+        f, g, h = ctx.saved_tensors
+        gf, gg, gh = (torch.empty_like(f) if need else None for need in needs[:3])
+        if any(o is not None for o in (gf, gg, gh)):
+            ctx.backend._sde_kl_backward(gf, gg, gh, None, gacc, f, g, h, ctx.dt, 0.0, 0, 0)
+        return (None, None, gf, gg, gh, gacc if needs[3] else None)

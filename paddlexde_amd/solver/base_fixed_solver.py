@@ -21,8 +21,8 @@ from ..xde.base_dde import DDE_DAMPING, BaseDDE
 from ..xde.base_ode import BaseODE
 from ..xde.base_sde import BaseSDE
 from ..xde.base_xde import BaseXDE
-from ._autograd import (CombineFn, InterpRowsFn, SdeEulerFn, SdeMilsteinFn, SdeRheunCorrectFn, SdeRheunPredictFn, SdeSrkStage1Fn, SdeSrkStage2Fn,
-                        SdeSrkStepFn, SdeSupportFn)
+from ._autograd import (CombineFn, InterpRowsFn, SdeEulerFn, SdeKlAccFn, SdeKlEulerFn, SdeMilsteinFn, SdeRheunCorrectFn, SdeRheunPredictFn,
+                        SdeSrkStage1Fn, SdeSrkStage2Fn, SdeSrkStepFn, SdeSupportFn)
 from ._common import as_operand, np_dtype, storage_ptr, t_span_to_host, upload
 
 _one_third = 1 / 3
@@ -122,14 +122,19 @@ class FixedSolver(metaclass=abc.ABCMeta):
     order: int
 
     steps_sde = False  # the step is a convergent scheme for SDEs (a BaseSDE problem): Euler, as Euler-Maruyama, Milstein and SRK (Ito), ReversibleHeun (Stratonovich)
+    steps_logqp = False  # the SDE step also accumulates the KL term of a latent SDE (sdeint's options logqp / prior_drift): Euler, Milstein
+    logqp_refusal = "its step has no KL accumulation"  # why not, where steps_sde and not steps_logqp (SRK, ReversibleHeun)
 
     graphable = True  # the step's control flow does not depend on data (False: AdamsBashforthMoulton)
     GRAPH_MIN_STEPS = 4
     AUTO_GRAPH_MIN_STEPS = 24  # pipeline="auto": steps needed to amortise a capture (~2 ms against ~100 us saved per step)
     AUTO_GRAPH_MAX_BYTES = 8 << 20  # ... and only for launch-bound (small) states
 
-    def __init__(self, xde, y0, step_size=None, grid_constructor=None, interp="linear", perturb=False, pipeline="auto", **kwargs):
+    def __init__(self, xde, y0, step_size=None, grid_constructor=None, interp="linear", perturb=False, pipeline="auto", logqp=False,
+                 **kwargs):
         self.xde = xde
+        self._logqp = bool(logqp)
+        self.logqp = None  # what the last walk accumulated: the KL term per output interval (``_walk``)
         self.y0 = y0
         self.dtype = y0.dtype
         self.step_size = step_size
@@ -186,6 +191,14 @@ class FixedSolver(metaclass=abc.ABCMeta):
                 raise NotImplementedError("interp='cubic' needs the derivative at both ends of a step, which an SDE path does not "
                                           "have; use interp='linear'")
             self._damping = 0.0
+            if self._logqp and not self.steps_logqp:
+                raise NotImplementedError(
+                    "{} does not accumulate logqp: {}; use solver=Euler (one fused launch per step) or solver=Milstein".format(
+                        type(self).__name__, self.logqp_refusal))
+            if self._logqp and getattr(xde, "h", None) is None:
+                raise ValueError("logqp needs the prior drift: BaseSDE(..., prior=h) (sdeint: options={'logqp': True, 'prior_drift': h})")
+        elif self._logqp:
+            raise NotImplementedError("logqp is the KL term of a latent SDE: only sdeint(..., solver=Euler) or solver=Milstein accumulate it")
         elif fuse_impl is BaseODE.fuse:
             self._damping = 0.0
         elif fuse_impl is BaseDDE.fuse:
@@ -197,6 +210,7 @@ class FixedSolver(metaclass=abc.ABCMeta):
         self.nfe = 0
         self._tdev_cache = {}
         self._carry = None  # ReversibleHeun: the (yh, fh, gh) the last step left
+        self._acc = None  # logqp: the running KL sum of every row the last step left (float64 y0.shape[:-1]; None: zero)
 
     # -- per-step state ---------------------------------------------------------------------------
     def _arm(self, dt=None, t0_host=None, row=None, y1_out=None, k=None, ctrls=None, rec=None):
@@ -267,11 +281,42 @@ class FixedSolver(metaclass=abc.ABCMeta):
         normals of (xde.seed, grid step k) — one xde_sde_em_step launch (SdeEulerFn when an operand is differentiated).  Returns
         ``(y1, f)``."""
         f, g, dt, s, _, _, k, grad = self._sde_prologue(t0, dtt, y0, dt)
+        if self._logqp:
+            return self._kl_em_step(t0, y0, f, g, dt, s, k, grad), f
         if grad:
             return SdeEulerFn.apply(self.backend, dt, s, self.xde.seed, k, y0, f, g), f
         out = self._y1_out if self._y1_out is not None else torch.empty_like(y0)
         self.backend._sde_em_step(out, y0, f, g, dt, s, self.xde.seed, k)
         return out, f
+
+    def _kl_em_step(self, t0, y0, f, g, dt, s, k, grad):
+        """The Euler-Maruyama step of a latent SDE (``logqp``): the prior drift ``h = prior(t0, y0)`` next to ``f`` and ``g``, and ONE
+        xde_sde_kl_step launch in the place of xde_sde_em_step — the same ``y1`` bit for bit, and the running KL sum of every row
+        (``self._acc``: float64 ``y0.shape[:-1]``, None before the first step) advanced by ``sum(((f - h)/g)**2, -1) * (0.5*dt)``.
+        Through SdeKlEulerFn when an operand is differentiated.  Returns ``y1``."""
+        h = as_operand(self.xde.prior(t0, y0), like=y0)
+        acc0 = self._acc
+        if grad or (torch.is_grad_enabled() and (h.requires_grad or (acc0 is not None and acc0.requires_grad))):
+            y1, self._acc = SdeKlEulerFn.apply(self.backend, dt, s, self.xde.seed, k, y0, f, g, h, acc0)
+            return y1
+        out = self._y1_out if self._y1_out is not None else torch.empty_like(y0)
+        acc1 = torch.empty(y0.shape[:-1], dtype=torch.float64, device=y0.device)
+        self.backend._sde_kl_step(out, acc1, y0, f, g, h, acc0, dt, s, self.xde.seed, k)
+        self._acc = acc1
+        return out
+
+    def _kl_accumulate(self, t0, y0, f, g, dt):
+        """The KL sum of a latent SDE advanced over a step whose state update has launches of its own (Milstein: the KL column has zero
+        diffusion, so its Milstein update is the Euler one): ``h = prior(t0, y0)`` and one accumulate-only xde_sde_kl_step launch, which
+        reads ``f, g, h`` only.  Through SdeKlAccFn when an operand is differentiated."""
+        h = as_operand(self.xde.prior(t0, y0), like=y0)
+        acc0 = self._acc
+        if torch.is_grad_enabled() and (f.requires_grad or g.requires_grad or h.requires_grad or (acc0 is not None and acc0.requires_grad)):
+            self._acc = SdeKlAccFn.apply(self.backend, dt, f, g, h, acc0)
+            return
+        acc1 = torch.empty(y0.shape[:-1], dtype=torch.float64, device=y0.device)
+        self.backend._sde_kl_step(None, acc1, None, f, g, h, acc0, dt, 0.0, 0, 0)
+        self._acc = acc1
 
     def _milstein_step(self, t0, dtt, y0, dt):
         """One derivative-free Milstein step of a BaseSDE (Kloeden & Platen's explicit strong order 1.0 scheme, Ito, diagonal noise):
@@ -285,12 +330,17 @@ class FixedSolver(metaclass=abc.ABCMeta):
         if grad:
             yb = SdeSupportFn.apply(self.backend, dt, s, y0, f, g)
             gb = as_operand(self.xde.diffusion(t0, yb), like=y0)
-            return SdeMilsteinFn.apply(self.backend, dt, s, c, self.xde.seed, k, y0, f, g, gb), f
+            y1 = SdeMilsteinFn.apply(self.backend, dt, s, c, self.xde.seed, k, y0, f, g, gb)
+            if self._logqp:
+                self._kl_accumulate(t0, y0, f, g, dt)
+            return y1, f
         yb = torch.empty_like(y0)
         self.backend._sde_milstein_support(yb, y0, f, g, dt, s)
         gb = as_operand(self.xde.diffusion(t0, yb), like=y0)
         out = self._y1_out if self._y1_out is not None else torch.empty_like(y0)
         self.backend._sde_milstein_step(out, y0, f, g, gb, dt, s, c, self.xde.seed, k)
+        if self._logqp:  # (after the step's own two launches, which stay as they are; y0 is not the step's output buffer)
+            self._kl_accumulate(t0, y0, f, g, dt)
         return out, f
 
     def _srk_step(self, t0, t1, dtt, t34, t14, y0, dt):
@@ -471,9 +521,14 @@ class FixedSolver(metaclass=abc.ABCMeta):
         out = torch.empty(*lead, pred_len * L, D, dtype=y0.dtype, device=y0.device)
         direct = (int(np.prod(lead)) == 1) if len(lead) else True  # output rows are contiguous slices
         out.narrow(-2, 0, L).copy_(y0)
+        # logqp: the cumulative KL sum of every row at every output time (float64; [0] is zero), from the steps' running sums
+        self._acc, self.logqp = None, None
+        cum = [torch.zeros(y0.shape[:-1], dtype=torch.float64, device=y0.device)] + [None] * (pred_len - 1) if self._logqp else None
         if n_steps == 0:  # a one-point grid (every output time is t[0]): every row is y0, as the plain walk's zero-length steps give
             for j in range(1, pred_len):
                 out.narrow(-2, j * L, L).copy_(y0)
+            if cum is not None:
+                self.logqp = self._logqp_intervals([cum[0]] * pred_len, y0)
             return out
 
         # pipeline="graph": one captured step replayed over the grid (no autograd, data-independent step).  "auto" (default)
@@ -494,7 +549,11 @@ class FixedSolver(metaclass=abc.ABCMeta):
 
         cubic = self.interp == "cubic"
         # (the plain walk makes a state per step; a hook may keep the states it is handed, and autograd keeps them anyway)
-        bufs = None if (plan.plain or tracking or self._step_end_hook) else (torch.empty_like(y0), torch.empty_like(y0))
+        # (logqp in grad mode: the prior's autograd graph may keep the state it was evaluated at even where the step itself is not
+        # differentiated — y0, drift and diffusion without a gradient — so every step makes a state of its own: neither a hand-over
+        # buffer, which a later step's kernel would overwrite behind autograd's back, nor a slice of the solution)
+        own_state = self._logqp and torch.is_grad_enabled()
+        bufs = None if (plan.plain or tracking or self._step_end_hook or own_state) else (torch.empty_like(y0), torch.empty_like(y0))
         y = y0
         try:
             for k in range(n_steps):
@@ -504,9 +563,12 @@ class FixedSolver(metaclass=abc.ABCMeta):
                 if jb is not None:
                     dst = out.narrow(-2, jb * L, L)
                     dst_b = dst.view(y0.shape) if (direct and dst.data_ptr() % 16 == 0) else None
-                y1_out = dst_b if dst_b is not None else (bufs[k % 2] if bufs is not None else None)
+                y1_out = None if own_state else (dst_b if dst_b is not None else (bufs[k % 2] if bufs is not None else None))
                 self._arm(grid[k + 1] - grid[k], grid[k], table[k] if table is not None else None, y1_out, k)
+                acc_a = self._acc
                 y1, f_a = self.step(t0, t1, y)
+                if cum is not None:
+                    self._logqp_rows(cum, rows, acc_a, self._acc)
                 if rows:
                     f_b = None
                     if cubic:
@@ -525,7 +587,32 @@ class FixedSolver(metaclass=abc.ABCMeta):
                 y = y1
         finally:
             self._arm()
+            self._acc = None
+        if cum is not None:
+            self.logqp = self._logqp_intervals(cum, y0)
         return out
+
+    @staticmethod
+    def _logqp_rows(cum, rows, acc_a, acc_b):
+        """The cumulative KL sum at the output rows ``(j, kind, w)`` of one grid step, from the running sums at its start (``acc_a``;
+        None: zero) and end: a row at either end takes that sum, a row strictly inside takes ``acc_a + w*(acc_b - acc_a)`` with the
+        linear weight the state's row takes — the scheme's integrand is constant over a step, so that is exact for the scheme.
+        ``[rows]``-sized float64 framework arithmetic, off the hot path."""
+        for j, kind, w in rows:
+            if kind == _hip.XDE_ROW_COPY_B:
+                cum[j] = acc_b
+            elif kind == _hip.XDE_ROW_COPY_A:
+                cum[j] = acc_a if acc_a is not None else torch.zeros_like(acc_b)
+            else:
+                cum[j] = acc_b * float(w[0]) if acc_a is None else acc_a + float(w[0]) * (acc_b - acc_a)
+
+    @staticmethod
+    def _logqp_intervals(cum, y0):
+        """``logqp[..., i] = L(t_{i+1}) - L(t_i)`` from the cumulative sums ``cum`` (float64), in the state dtype: ``y0.shape[:-1] +
+        (T - 1,)``."""
+        if len(cum) < 2:
+            return torch.zeros(y0.shape[:-1] + (0,), dtype=y0.dtype, device=y0.device)
+        return torch.stack([b - a for a, b in zip(cum[:-1], cum[1:])], dim=-1).to(y0.dtype)
 
     def _write_rows(self, out, L, rows, y_a, y_b, f_a=None, f_b=None):
         """Rows ``(j, kind, w)`` of one grid step of a sub-stepped plan into ``out`` (``[..., T*L, D]``).  Through InterpRowsFn when an

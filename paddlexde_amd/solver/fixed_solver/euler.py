@@ -7,6 +7,7 @@ from ..base_fixed_solver import FixedSolver
 class Euler(FixedSolver):
     order = 1
     steps_sde = True  # a BaseSDE is stepped as Ito Euler-Maruyama (FixedSolver._em_step)
+    steps_logqp = True  # ... and with logqp by the fused step + KL launch (FixedSolver._kl_em_step)
 
     time_values = ((1.0, False),)  # dt
 

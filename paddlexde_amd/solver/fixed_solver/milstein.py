@@ -6,6 +6,7 @@ from ..base_fixed_solver import FixedSolver
 class Milstein(FixedSolver):
     order = 1
     steps_sde = True
+    steps_logqp = True  # (its two launches, and one accumulate-only launch: FixedSolver._kl_accumulate)
 
     time_values = ((1.0, False),)  # dt
 

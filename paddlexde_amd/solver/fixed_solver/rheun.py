@@ -12,6 +12,7 @@ class ReversibleHeun(FixedSolver):
 
     order = 1
     steps_sde = True
+    logqp_refusal = "its drift is the mean of two evaluations, one of them carried over from the step before, so the KL term would need the prior drift at both"
 
     time_values = ((1.0, False),)  # dt
 

@@ -8,6 +8,7 @@ class SRK(FixedSolver):
 
     order = 1.5
     steps_sde = True
+    logqp_refusal = "its drift is a two-stage mean, so the KL term would need the prior drift at the second stage as well"
 
     time_values = ((1.0, False), (0.75, True), (0.25, True))  # dt, t0 + 3/4 dt, t0 + 1/4 dt
 

@@ -31,12 +31,13 @@ def check_seed(seed):
 
 
 class BaseSDE(BaseXDE):
-    def __init__(self, f, g, y0, t_span, reverse=False, seed=None):
+    def __init__(self, f, g, y0, t_span, reverse=False, seed=None, prior=None):
         super().__init__(name="SDE", var_nums=2, y0=y0, t_span=t_span)
         if isinstance(y0, (tuple, list)):
             raise NotImplementedError("BaseSDE takes a tensor y0, not a tuple: stack the members into one state tensor")
         self.__dict__["f"] = f  # (plain attributes: see BaseXDE.__init__)
         self.__dict__["g"] = g
+        self.__dict__["h"] = prior  # the prior drift of a latent SDE (sdeint's options logqp / prior_drift), or None
         self.__dict__["seed"] = draw_seed() if seed is None else check_seed(seed)
         # `reverse` is accepted and has no effect, as in the reference (base_sde.py:40-41: `t_span.clip(0)`, result discarded)
         self.init_y0(y0)
@@ -55,6 +56,17 @@ class BaseSDE(BaseXDE):
             raise ValueError("the diffusion g(t, y) must return a tensor of y's shape {} and dtype {} (diagonal noise), got {}".format(
                 tuple(y.shape), y.dtype, got))
         return g
+
+    def prior(self, t, y):
+        """``h(t, y)``, the prior drift of a latent SDE, checked as ``diffusion`` checks ``g``: a tensor of y's shape and dtype."""
+        if self.h is None:
+            raise ValueError("this BaseSDE has no prior drift: pass prior= (sdeint: options={'logqp': True, 'prior_drift': h})")
+        h = self.h(t, y)
+        if not torch.is_tensor(h) or h.shape != y.shape or h.dtype != y.dtype:
+            got = "{} {}".format(tuple(h.shape), h.dtype) if torch.is_tensor(h) else type(h).__name__
+            raise ValueError("the prior drift h(t, y) must return a tensor of y's shape {} and dtype {}, got {}".format(
+                tuple(y.shape), y.dtype, got))
+        return h
 
     def move(self, t0, dt, y0):
         """base_sde.py:43-58 — the drift and the diffusion at (t0, y0); the solver draws the increment."""
