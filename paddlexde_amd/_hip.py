@@ -260,8 +260,15 @@ KL_PROTOTYPES = {
     "xde_sde_kl_step": (_i32, [_vp] * 7 + [_i64, _i64, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
     "xde_sde_kl_backward": (_i32, [_vp] * 8 + [_i64, _i64, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
 }
+# the entry points of include/xde_hip_gn.h (the Euler-Maruyama step with general or scalar noise, and its cotangents); bound by
+# load_library() after _bind_kl
+GN_PROTOTYPES = {
+    "xde_sde_gn_step": (_i32, [_vp] * 4 + [_i64, _i64, _i64, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
+    "xde_sde_gn_backward": (_i32, [_vp] * 3 + [_i64, _i64, _i64, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
+}
 SYMBOLS = tuple(PROTOTYPES)
 KL_SYMBOLS = tuple(KL_PROTOTYPES)
+GN_SYMBOLS = tuple(GN_PROTOTYPES)
 BACKPROP_SYMBOLS = tuple(BACKPROP_PROTOTYPES)
 GRID_SYMBOLS = tuple(GRID_PROTOTYPES)
 SDE_SYMBOLS = tuple(SDE_PROTOTYPES)
@@ -300,7 +307,7 @@ _REBUILD = "rebuild it with `python -m paddlexde_amd.csrc.build --force`"
 
 
 def _declare(lib, sym):
-    proto = PROTOTYPES.get(sym) or BACKPROP_PROTOTYPES.get(sym) or GRID_PROTOTYPES.get(sym) or SDE_PROTOTYPES.get(sym) or CDE_PROTOTYPES.get(sym) or SEAM_PROTOTYPES.get(sym) or SPLINE_PROTOTYPES.get(sym) or CDEGRAD_PROTOTYPES.get(sym) or KL_PROTOTYPES[sym]
+    proto = PROTOTYPES.get(sym) or BACKPROP_PROTOTYPES.get(sym) or GRID_PROTOTYPES.get(sym) or SDE_PROTOTYPES.get(sym) or CDE_PROTOTYPES.get(sym) or SEAM_PROTOTYPES.get(sym) or SPLINE_PROTOTYPES.get(sym) or CDEGRAD_PROTOTYPES.get(sym) or KL_PROTOTYPES.get(sym) or GN_PROTOTYPES[sym]
     try:
         fn = getattr(lib, sym)
     except AttributeError:
@@ -370,6 +377,12 @@ def _bind_kl(lib):
         _declare(lib, sym)
 
 
+def _bind_gn(lib):
+    """Declare the entry points of include/xde_hip_gn.h on ``lib`` (after ``_bind``: the ABI check comes first)."""
+    for sym in GN_SYMBOLS:
+        _declare(lib, sym)
+
+
 def load_library():
     """dlopen libxde_hip.so and declare prototypes.  Raises if it has not been built, or is not the library this binding speaks to."""
     global _lib
@@ -392,6 +405,7 @@ def load_library():
         _bind_spline(lib)
         _bind_cdegrad(lib)
         _bind_kl(lib)
+        _bind_gn(lib)
         _lib = lib
     return _lib
 
@@ -1038,6 +1052,49 @@ class HipBackend:
         rows, D, tail = self._kl_call("_sde_kl_backward", (gf, gg, gh, gy1, f, g, h), (gacc,), f, float(dt), float(s), int(seed), int(k))
         rc = self.lib.xde_sde_kl_backward(_ptr(gf), _ptr(gg), _ptr(gh), _ptr(gy1), _ptr(gacc), _ptr(f), _ptr(g), _ptr(h), rows, D, *tail)
         self._check(rc, "xde_sde_kl_backward")
+
+    # -- the Euler-Maruyama step with general or scalar noise (include/xde_hip_gn.h) ---------------------------------------------------
+    # Private for the reason _sde_em_step is.  Only FixedSolver._em_step under a non-diagonal BaseSDE (and its autograd node) call these.
+    def _gn_call(self, who, state, mats, like, *scalars):
+        """The operand check the two general-noise entry points share; nothing is launched here.  ``state`` must be contiguous device
+        tensors of ``like``'s shape ``[.., D]`` and dtype and ``mats`` contiguous device tensors of shape ``[.., D, M]`` and that dtype,
+        one M for all; None stands for a null pointer and is not checked (``like`` and one of ``mats`` are never None).  Returns
+        ``(rows, D, M, tail)``, ``tail`` being ``scalars`` followed by the dtype code and the stream."""
+        self._require_device(*state, *mats)
+        if like.dim() < 1:
+            raise XdeError("{}: the state needs a last axis".format(who))
+        for x in state:
+            if x is not None and (not x.is_contiguous() or x.shape != like.shape or x.dtype != like.dtype):
+                raise XdeError("{}: the state operands must be contiguous tensors of one shape and dtype".format(who))
+        M = None
+        for x in mats:
+            if x is None:
+                continue
+            if not x.is_contiguous() or x.dtype != like.dtype or x.shape[:-1] != like.shape or x.shape[-1] < 1:
+                raise XdeError("{}: the diffusion operand must be a contiguous tensor of shape {} + (M,), M >= 1, and dtype {}, got {} {}".format(
+                    who, tuple(like.shape), like.dtype, tuple(x.shape), x.dtype))
+            M = x.shape[-1]
+        D = like.shape[-1]
+        rows = like.numel() // D if D else 0
+        return rows, D, M, scalars + (dtype_code(like.dtype), self._stream(like))
+
+    def _sde_gn_step(self, y1, y0, f, g, dt, s, seed, k):
+        """``y1[.., d] = (y0[.., d] + f[.., d]*dt) + sum_m g[.., d, m]*(s*Z[.., m])``, the sum sequential in m, with Z the normals of
+        (``seed``, step ``k``) over the flat ``[rows, M]`` array; ``g`` is ``[.., D, M]``; ``y1`` may be ``y0``.  One launch."""
+        rows, D, M, tail = self._gn_call("_sde_gn_step", (y1, y0, f), (g,), y0, float(dt), float(s), int(seed), int(k))
+        if rows == 0:
+            return
+        self._check(self.lib.xde_sde_gn_step(_ptr(y1), _ptr(y0), _ptr(f), _ptr(g), rows, D, M, *tail), "xde_sde_gn_step")
+
+    def _sde_gn_backward(self, gf, gg, gy1, M, dt, s, seed, k):
+        """``gf = gy1*dt`` (``[.., D]``) and ``gg[.., d, m] = gy1[.., d]*(s*Z[.., m])`` (``[.., D, M]``); either may be None: skipped.
+        One launch regenerating the forward's Z."""
+        rows, D, M_, tail = self._gn_call("_sde_gn_backward", (gf, gy1), (gg,), gy1, float(dt), float(s), int(seed), int(k))
+        if M_ is not None and M_ != int(M):
+            raise XdeError("_sde_gn_backward: gg's last axis is {}, M is {}".format(M_, int(M)))
+        if rows == 0:
+            return
+        self._check(self.lib.xde_sde_gn_backward(_ptr(gf), _ptr(gg), _ptr(gy1), rows, D, int(M), *tail), "xde_sde_gn_backward")
 
     # -- the seam between two attempts as one resident launch (include/xde_hip_seam.h) ------------------------------------------------
     # Private for the reason _interp_rows is: the public methods are the contract tests/_cpu_double.py mirrors.  Only AdaptiveRKSolver

@@ -20,7 +20,7 @@ import torch
 
 from ..solver.base_fixed_solver import FixedSolver
 from ..utils.ode_utils import _rms_norm
-from ..xde.base_sde import BaseSDE
+from ..xde.base_sde import BaseSDE, check_noise_type
 
 
 def sdeint(
@@ -47,7 +47,16 @@ def sdeint(
     ``[t[i], t[i+1]]`` between the path's law and that of ``dy = h(t, y) dt + diffusion(t, y) dW``: the scheme's sum of
     ``0.5 * |(drift - h) / diffusion|**2 * dt`` over the last axis, accumulated in float64 by the step launch itself
     (include/xde_hip_kl.h).  ``h(t, y)`` returns a tensor of ``y``'s shape and dtype; ``diffusion`` must be non-zero.  Gradients reach
-    ``y0`` and the parameters of all three functions, from ``ys`` and from ``logqp``."""
+    ``y0`` and the parameters of all three functions, from ``ys`` and from ``logqp``.
+
+    ``options={"noise_type": "general"}`` (``solver=Euler``): ``diffusion(t, y)`` returns a tensor of shape ``y.shape + (M,)`` and
+    ``y``'s dtype, ``M >= 1`` fixed by its first evaluation, and every row of the state (its last axis, D elements) is driven by an
+    M-dimensional Brownian motion through its ``[D, M]`` matrix: ``y1 = (y0 + f*dt) + g @ (sqrt(|dt|) * Z)``, Z one normal per row and
+    m, the sum over m taken sequentially.  One xde_sde_gn_step launch per step streams ``g`` once and builds the increment on chip; the
+    backward is one launch that regenerates Z and keeps nothing of the forward but ``(dt, seed, k)`` (include/xde_hip_gn.h).
+    ``"scalar"`` is general noise with ``M == 1`` (``diffusion`` returns ``y.shape + (1,)``); ``"diagonal"``, the default, is the
+    element-wise noise described above, unchanged.  Any other value is a ``ValueError``.  Milstein, SRK, ReversibleHeun,
+    ``sdeint_adjoint`` and ``logqp`` take diagonal noise only and say so."""
     if isinstance(y0, (tuple, list)):
         raise NotImplementedError("sdeint takes a tensor y0, not a tuple: stack the members into one state tensor")
     if not (isinstance(solver, type) and issubclass(solver, FixedSolver)):
@@ -62,6 +71,7 @@ def sdeint(
     seed = options.pop("seed", None)
     logqp = bool(options.pop("logqp", False))
     prior = options.pop("prior_drift", None)
+    noise_type = check_noise_type(options.pop("noise_type", "diagonal"))
     if logqp and prior is None:
         raise ValueError("options['logqp'] needs the prior drift: options={'logqp': True, 'prior_drift': h} with h(t, y) a tensor of y's "
                          "shape and dtype (the KL term is between dy = drift dt + diffusion dW and dy = h dt + diffusion dW)")
@@ -69,7 +79,7 @@ def sdeint(
         raise ValueError("options['prior_drift'] is only read with options['logqp'] = True (sdeint then returns (ys, logqp)); drop it, "
                          "or ask for logqp")
 
-    xde = BaseSDE(f=drift, g=diffusion, y0=y0, t_span=t, reverse=reverse, seed=seed, prior=prior)
+    xde = BaseSDE(f=drift, g=diffusion, y0=y0, t_span=t, reverse=reverse, seed=seed, prior=prior, noise_type=noise_type)
 
     if logqp:
         options["logqp"] = True  # (refused by the solvers whose step cannot accumulate it, before the first launch)

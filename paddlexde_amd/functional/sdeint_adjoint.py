@@ -20,7 +20,7 @@ from ..solver._common import as_operand
 from ..solver.base_fixed_solver import sde_step_scalars
 from ..solver.fixed_solver.rheun import ReversibleHeun
 from ..utils.ode_utils import _rms_norm
-from ..xde.base_sde import BaseSDE
+from ..xde.base_sde import BaseSDE, check_noise_type
 
 _MESSAGE = (
     "sdeint_adjoint is not implemented (the stochastic adjoint needs a Brownian path that can be queried backwards in time); "
@@ -32,6 +32,7 @@ def _solve(drift, diffusion, y0, t, rtol, atol, options):
     """The forward of ``sdeint(..., solver=ReversibleHeun)`` and what the sweep needs of it."""
     options = dict(options)
     seed = options.pop("seed", None)
+    options.pop("noise_type", None)  # ("diagonal": sdeint_adjoint has refused any other value)
     xde = BaseSDE(f=drift, g=diffusion, y0=y0, t_span=t, seed=seed)
     solver = ReversibleHeun(xde=xde, y0=xde.y0, rtol=rtol, atol=atol, **options)
     grid, grid_dev, plan, pred_len = solver._plan(t)
@@ -177,6 +178,11 @@ def sdeint_adjoint(
             raise NotImplementedError("sdeint_adjoint does not take options[{!r}]: the KL term of a latent SDE is accumulated by "
                                       "sdeint(..., solver=Euler) or solver=Milstein, which keep the steps' operands for the "
                                       "backward".format(key))
+    noise_type = check_noise_type(dict(options).get("noise_type", "diagonal"))
+    if noise_type != "diagonal":
+        raise NotImplementedError("sdeint_adjoint does not take options['noise_type'] = {!r}: the reversible Heun kernels and their "
+                                  "cotangent sweep are diagonal (general noise for them is a follow-up); sdeint(..., solver=Euler) "
+                                  "steps general and scalar noise and keeps the steps' operands for the backward".format(noise_type))
     if solver is not ReversibleHeun:
         raise NotImplementedError(_MESSAGE)
     for name, value in (("adjoint_solver", adjoint_solver), ("adjoint_rtol", adjoint_rtol), ("adjoint_atol", adjoint_atol),

@@ -1,4 +1,4 @@
-"""Autograd nodes around the step kernels (xde_stage_combine, xde_interp_rows, xde_sde_em_step, xde_sde_milstein_step, xde_sde_srk_*, xde_sde_rheun_*, xde_sde_kl_*) for discretise-then-optimise training.
+"""Autograd nodes around the step kernels (xde_stage_combine, xde_interp_rows, xde_sde_em_step, xde_sde_milstein_step, xde_sde_srk_*, xde_sde_rheun_*, xde_sde_kl_*, xde_sde_gn_*) for discretise-then-optimise training.
 
 The reference trains by back-propagating through its eager solver ops (example/ode_demo.py:51-53:
 ``pred_y = odeint(func, batch_y0, t_span, solver=RK4); loss.backward()``).  Here the forward is one combine launch
@@ -124,6 +124,31 @@ class SdeEulerFn(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, g):
         return (None,) * 5 + _sde_backward(ctx.backend._sde_em_backward, g, ctx.needs_input_grad[5:8], ctx.meta)
+
+
+class SdeGnEulerFn(torch.autograd.Function):
+    """One Euler-Maruyama step with general or scalar noise, ``y1[.., d] = (y0 + f*dt)[.., d] + sum_m g[.., d, m]*(s*Z[.., m])``
+    (``HipBackend._sde_gn_step``), as an autograd node.  The node keeps only ``(dt, s, seed, k)`` and M: backward is one
+    xde_sde_gn_backward launch that regenerates Z and writes ``gf = gy1*dt`` and ``gg[.., d, m] = gy1[.., d]*(s*Z[.., m])``, each only
+    if wanted (an unwanted cotangent stays None); ``gy0 = gy1`` needs no launch."""
+
+    @staticmethod
+    def forward(ctx, backend, dt, s, seed, k, y0, f, g):
+        out = torch.empty_like(y0)
+        backend._sde_gn_step(out, y0.detach(), f.detach(), g.detach(), dt, s, seed, k)
+        ctx.backend, ctx.meta, ctx.M = backend, (float(dt), float(s), int(seed), int(k)), int(g.shape[-1])
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        need_y, need_f, need_g = ctx.needs_input_grad[5:8]
+        gy = _cotangent(gy)
+        gf = torch.empty_like(gy) if need_f else None
+        gg = torch.empty(tuple(gy.shape) + (ctx.M,), dtype=gy.dtype, device=gy.device) if need_g else None
+        if gf is not None or gg is not None:
+            ctx.backend._sde_gn_backward(gf, gg, gy, ctx.M, *ctx.meta)
+        return (None,) * 5 + (gy if need_y else None, gf, gg)
 
 
 class SdeSupportFn(torch.autograd.Function):

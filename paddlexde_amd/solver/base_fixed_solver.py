@@ -21,7 +21,7 @@ from ..xde.base_dde import DDE_DAMPING, BaseDDE
 from ..xde.base_ode import BaseODE
 from ..xde.base_sde import BaseSDE
 from ..xde.base_xde import BaseXDE
-from ._autograd import (CombineFn, InterpRowsFn, SdeEulerFn, SdeKlAccFn, SdeKlEulerFn, SdeMilsteinFn, SdeRheunCorrectFn, SdeRheunPredictFn,
+from ._autograd import (CombineFn, InterpRowsFn, SdeEulerFn, SdeGnEulerFn, SdeKlAccFn, SdeKlEulerFn, SdeMilsteinFn, SdeRheunCorrectFn, SdeRheunPredictFn,
                         SdeSrkStage1Fn, SdeSrkStage2Fn, SdeSrkStepFn, SdeSupportFn)
 from ._common import as_operand, np_dtype, storage_ptr, t_span_to_host, upload
 
@@ -124,6 +124,9 @@ class FixedSolver(metaclass=abc.ABCMeta):
     steps_sde = False  # the step is a convergent scheme for SDEs (a BaseSDE problem): Euler, as Euler-Maruyama, Milstein and SRK (Ito), ReversibleHeun (Stratonovich)
     steps_logqp = False  # the SDE step also accumulates the KL term of a latent SDE (sdeint's options logqp / prior_drift): Euler, Milstein
     logqp_refusal = "its step has no KL accumulation"  # why not, where steps_sde and not steps_logqp (SRK, ReversibleHeun)
+    steps_matrix_noise = False  # the SDE step takes general and scalar noise (BaseSDE(..., noise_type=...)): Euler (xde_sde_gn_step)
+    # why not, where steps_sde and not steps_matrix_noise (Milstein and SRK; ReversibleHeun states its own)
+    matrix_noise_refusal = "its scheme assumes commutative, diagonal noise; for a [D, M] diffusion it would need Levy areas"
 
     graphable = True  # the step's control flow does not depend on data (False: AdamsBashforthMoulton)
     GRAPH_MIN_STEPS = 4
@@ -180,6 +183,7 @@ class FixedSolver(metaclass=abc.ABCMeta):
         # Euler-Maruyama update is xde_sde_em_step (Milstein adds its correction to it: xde_sde_milstein_step; SRK is xde_sde_srk_*)
         fuse_impl = getattr(type(xde), "fuse", None)
         self._sde = fuse_impl is BaseSDE.fuse
+        self._matrix_noise = False  # SDE: the diffusion is a [D, M] matrix per row (BaseSDE's noise_type "general" or "scalar")
         if self._sde:
             if not self.steps_sde:
                 raise NotImplementedError("{} does not step SDEs: its tableau does not converge for Ito SDEs; use Euler "
@@ -191,6 +195,14 @@ class FixedSolver(metaclass=abc.ABCMeta):
                 raise NotImplementedError("interp='cubic' needs the derivative at both ends of a step, which an SDE path does not "
                                           "have; use interp='linear'")
             self._damping = 0.0
+            self._matrix_noise = getattr(xde, "noise_type", "diagonal") != "diagonal"
+            if self._matrix_noise and not self.steps_matrix_noise:
+                raise NotImplementedError("{} does not step {} noise: {}; solver=Euler steps general and scalar noise (one fused launch "
+                                          "per step)".format(type(self).__name__, xde.noise_type, self.matrix_noise_refusal))
+            if self._matrix_noise and self._logqp:
+                raise NotImplementedError("logqp takes diagonal noise only: with a [D, M] diffusion (f - h)/g would become a linear solve "
+                                          "per row; solver=Euler steps general and scalar noise without logqp, and logqp with "
+                                          "noise_type='diagonal'")
             if self._logqp and not self.steps_logqp:
                 raise NotImplementedError(
                     "{} does not accumulate logqp: {}; use solver=Euler (one fused launch per step) or solver=Milstein".format(
@@ -267,7 +279,7 @@ class FixedSolver(metaclass=abc.ABCMeta):
         Python floats."""
         self.nfe += 1
         f, g = self.move(t0, dtt, y0)
-        f, g = as_operand(f, like=y0), as_operand(g, like=y0)
+        f, g = as_operand(f, like=y0), (as_operand(g) if self._matrix_noise else as_operand(g, like=y0))  # (general: [.., D, M])
         T = np_dtype(y0.dtype)
         root = np.sqrt(abs(np.float64(dt)))
         c = T(0.5 / root) if root > 0 else T(0.0)
@@ -278,9 +290,16 @@ class FixedSolver(metaclass=abc.ABCMeta):
 
     def _em_step(self, t0, dtt, y0, dt):
         """One Ito Euler-Maruyama step of a BaseSDE: ``y1 = (y0 + f*dt) + g*(s*Z)``, ``s = sqrt(|dt|)`` in the state dtype, Z the
-        normals of (xde.seed, grid step k) — one xde_sde_em_step launch (SdeEulerFn when an operand is differentiated).  Returns
-        ``(y1, f)``."""
+        normals of (xde.seed, grid step k) — one xde_sde_em_step launch (SdeEulerFn when an operand is differentiated).  Under general
+        or scalar noise ``g`` is ``[.., D, M]`` and the step is ``y1 = (y0 + f*dt) + sum_m g[.., m]*(s*Z[.., m])``, Z over the flat
+        ``[rows, M]`` array: one xde_sde_gn_step launch in its place (SdeGnEulerFn).  Returns ``(y1, f)``."""
         f, g, dt, s, _, _, k, grad = self._sde_prologue(t0, dtt, y0, dt)
+        if self._matrix_noise:
+            if grad:
+                return SdeGnEulerFn.apply(self.backend, dt, s, self.xde.seed, k, y0, f, g), f
+            out = self._y1_out if self._y1_out is not None else torch.empty_like(y0)
+            self.backend._sde_gn_step(out, y0, f, g, dt, s, self.xde.seed, k)
+            return out, f
         if self._logqp:
             return self._kl_em_step(t0, y0, f, g, dt, s, k, grad), f
         if grad:

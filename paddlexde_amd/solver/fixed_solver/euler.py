@@ -8,6 +8,7 @@ class Euler(FixedSolver):
     order = 1
     steps_sde = True  # a BaseSDE is stepped as Ito Euler-Maruyama (FixedSolver._em_step)
     steps_logqp = True  # ... and with logqp by the fused step + KL launch (FixedSolver._kl_em_step)
+    steps_matrix_noise = True  # ... and under general or scalar noise by xde_sde_gn_step, in the same place
 
     time_values = ((1.0, False),)  # dt
 

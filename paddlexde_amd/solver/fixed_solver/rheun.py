@@ -14,6 +14,8 @@ class ReversibleHeun(FixedSolver):
     steps_sde = True
     logqp_refusal = "its drift is the mean of two evaluations, one of them carried over from the step before, so the KL term would need the prior drift at both"
 
+    matrix_noise_refusal = "its predict, correct and adjoint kernels are diagonal (general noise for them is a follow-up)"
+
     time_values = ((1.0, False),)  # dt
 
     def __init__(self, xde, y0, **kwargs):
