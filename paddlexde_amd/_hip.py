@@ -19,6 +19,7 @@ XDE_F32, XDE_F64 = 0, 1
 XDE_MAX_K, XDE_MAX_SEG, XDE_MAX_STAGE = 14, 16, 13
 XDE_MAX_PACK = 64
 XDE_BP_MAX_X = XDE_MAX_K + 2  # operands of one xde_stage_cotangent launch
+XDE_ROWS_MAX_K = 7  # operands of one xde_rows_* launch (include/xde_hip_rows.h)
 XDE_P2P_MAX_RANKS, XDE_P2P_HANDLE_BYTES = 16, 64
 COMBINE_RK, COMBINE_FUSE, COMBINE_WFUSE = 0, 1, 2
 NORM_RMS, NORM_LINF = 0, 1
@@ -266,7 +267,31 @@ GN_PROTOTYPES = {
     "xde_sde_gn_step": (_i32, [_vp] * 4 + [_i64, _i64, _i64, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
     "xde_sde_gn_backward": (_i32, [_vp] * 3 + [_i64, _i64, _i64, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
 }
+
+
+class XdeRowsCtl(C.Structure):
+    """Mirror of xde_rows_ctl_t (include/xde_hip_rows.h): the planes of the per-row control block."""
+
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32)] + [(name, C.c_void_p) for name in (
+        "t", "t_prev", "h", "h_used", "ratio", "nonfinite", "accept", "done", "status", "next_out", "n_accept", "n_reject",
+        "steps_in_interval", "t_stage")]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.struct_size = C.sizeof(type(self))
+
+
+_rows_ctl = C.POINTER(XdeRowsCtl)
+# the entry points of include/xde_hip_rows.h (per-sample adaptive stepping: every row of the batch its own step); bound by
+# load_library() after _bind_gn
+ROWS_PROTOTYPES = {
+    "xde_rows_stage_combine": (_i32, [_vp, _vp, _vp, _vpp, _dp, _dp, _i32, _rows_ctl, _i64, _i64, _i32, _vp]),
+    "xde_rows_norm_control": (_i32, [_vpp, _dp, _i32, _vp, _vp, _vp, _rows_ctl, _params, _vp, C.c_int32, _i64, _i64, _i32, _vp]),
+    "xde_rows_dense_commit": (_i32, [_vp, _vpp, _dp, _i32, _vp, _vp, _vp, _vp, _rows_ctl, _params, _vp, C.c_int32, _i64, _i64, _i32, _vp]),
+    "xde_rows_scaled_norm": (_i32, [_vp, _vp, _vp, _vp, _dbl, _dbl, _i64, _i64, _i32, _vp]),
+}
 SYMBOLS = tuple(PROTOTYPES)
+ROWS_SYMBOLS = tuple(ROWS_PROTOTYPES)
 KL_SYMBOLS = tuple(KL_PROTOTYPES)
 GN_SYMBOLS = tuple(GN_PROTOTYPES)
 BACKPROP_SYMBOLS = tuple(BACKPROP_PROTOTYPES)
@@ -280,6 +305,28 @@ XDE_INTERP_MAX_ROWS = 8
 XDE_INTERP_LINEAR, XDE_INTERP_CUBIC = 0, 1
 XDE_ROW_INTERP, XDE_ROW_COPY_A, XDE_ROW_COPY_B = 0, 1, 2
 XDE_NOISE_NORMAL, XDE_NOISE_BITS = 0, 1
+
+
+class RowsCtl:
+    """The per-row control block of a per-sample solve (xde_rows_ctl_t): two tensors of planes and the stage times, with the
+    struct of their addresses the entry points take.  Allocated by torch on the state's device."""
+
+    F64 = ("t", "t_prev", "h", "h_used", "ratio", "nonfinite")
+    I32 = ("accept", "done", "status", "next_out", "n_accept", "n_reject", "steps_in_interval")
+
+    def __init__(self, rows, n_stage, state_dtype, device):
+        self.rows = int(rows)
+        self.f64 = torch.zeros(len(self.F64), self.rows, dtype=torch.float64, device=device)
+        self.i32 = torch.zeros(len(self.I32), self.rows, dtype=torch.int32, device=device)
+        self.t_stage = torch.zeros(int(n_stage), self.rows, dtype=state_dtype, device=device)
+        self.c = XdeRowsCtl()
+        for i, name in enumerate(self.F64):
+            setattr(self, name, self.f64[i])
+            setattr(self.c, name, self.f64[i].data_ptr())
+        for i, name in enumerate(self.I32):
+            setattr(self, name, self.i32[i])
+            setattr(self.c, name, self.i32[i].data_ptr())
+        self.c.t_stage = self.t_stage.data_ptr()
 
 
 class _Work:
@@ -307,7 +354,7 @@ _REBUILD = "rebuild it with `python -m paddlexde_amd.csrc.build --force`"
 
 
 def _declare(lib, sym):
-    proto = PROTOTYPES.get(sym) or BACKPROP_PROTOTYPES.get(sym) or GRID_PROTOTYPES.get(sym) or SDE_PROTOTYPES.get(sym) or CDE_PROTOTYPES.get(sym) or SEAM_PROTOTYPES.get(sym) or SPLINE_PROTOTYPES.get(sym) or CDEGRAD_PROTOTYPES.get(sym) or KL_PROTOTYPES.get(sym) or GN_PROTOTYPES[sym]
+    proto = PROTOTYPES.get(sym) or BACKPROP_PROTOTYPES.get(sym) or GRID_PROTOTYPES.get(sym) or SDE_PROTOTYPES.get(sym) or CDE_PROTOTYPES.get(sym) or SEAM_PROTOTYPES.get(sym) or SPLINE_PROTOTYPES.get(sym) or CDEGRAD_PROTOTYPES.get(sym) or KL_PROTOTYPES.get(sym) or GN_PROTOTYPES.get(sym) or ROWS_PROTOTYPES[sym]
     try:
         fn = getattr(lib, sym)
     except AttributeError:
@@ -383,6 +430,12 @@ def _bind_gn(lib):
         _declare(lib, sym)
 
 
+def _bind_rows(lib):
+    """Declare the entry points of include/xde_hip_rows.h on ``lib`` (after ``_bind``: the ABI check comes first)."""
+    for sym in ROWS_SYMBOLS:
+        _declare(lib, sym)
+
+
 def load_library():
     """dlopen libxde_hip.so and declare prototypes.  Raises if it has not been built, or is not the library this binding speaks to."""
     global _lib
@@ -406,6 +459,7 @@ def load_library():
         _bind_cdegrad(lib)
         _bind_kl(lib)
         _bind_gn(lib)
+        _bind_rows(lib)
         _lib = lib
     return _lib
 
@@ -1095,6 +1149,56 @@ class HipBackend:
         if rows == 0:
             return
         self._check(self.lib.xde_sde_gn_backward(_ptr(gf), _ptr(gg), _ptr(gy1), rows, D, int(M), *tail), "xde_sde_gn_backward")
+
+    # -- per-sample adaptive stepping (include/xde_hip_rows.h) ------------------------------------------------------------------------
+    # Private for the reason _interp_rows is.  Only solver/_rk_rows.py calls these.  ``ctl`` is a ``RowsCtl``.
+    def _rows_call(self, who, ctl, like, *operands):
+        """The operand check the four entry points share; nothing is launched here.  Returns ``(rows, D, dtype code, stream)``."""
+        self._require_device(like, ctl.f64, ctl.i32, ctl.t_stage, *operands)
+        if like.dim() < 2 or like.shape[0] != ctl.rows:
+            raise XdeError("{}: the state is [rows, ...] with rows = {} (got {})".format(who, ctl.rows, tuple(like.shape)))
+        for x in operands:
+            if x is not None and (not x.is_contiguous() or x.shape != like.shape or x.dtype != like.dtype):
+                raise XdeError("{}: the state operands must be contiguous tensors of one shape and dtype".format(who))
+        return ctl.rows, like.numel() // ctl.rows, dtype_code(like.dtype), self._stream(like)
+
+    def _rows_stage_combine(self, out, y0, ks, coef, ctl, *, out2=None, coef2=None):
+        """``out[r] = y0[r] + sum_j ks[j][r] * (coef[j] * h[r])``, XDE_COMBINE_RK's op order row by row; done rows: ``out = y0``."""
+        rows, D, code, st = self._rows_call("_rows_stage_combine", ctl, y0, out, out2, y0, *ks)
+        rc = self.lib.xde_rows_stage_combine(_ptr(out), _ptr(out2), _ptr(y0), _ptr_array(ks), _dbl_array(coef),
+                                             _dbl_array(coef2) if coef2 is not None else None, len(ks), C.byref(ctl.c), rows, D, code, st)
+        self._check(rc, "xde_rows_stage_combine")
+
+    def _rows_norm_control(self, ks, c_err, y0, y1, ctl, params, t_span_dev, *, e_pre=None):
+        """Per row: the error ratio, the controller's verdict and next step, the next attempt's stage times.  One launch."""
+        rows, D, code, st = self._rows_call("_rows_norm_control", ctl, y0, y0, y1, e_pre, *ks)
+        self._require_device(t_span_dev)
+        rc = self.lib.xde_rows_norm_control(_ptr_array(ks), _dbl_array(c_err), len(ks), _ptr(e_pre), _ptr(y0), _ptr(y1), C.byref(ctl.c),
+                                            C.byref(params), _ptr(t_span_dev), t_span_dev.numel(), rows, D, code, st)
+        self._check(rc, "xde_rows_norm_control")
+
+    def _rows_dense_commit(self, out, ks, mid, y0, y1, f1, ctl, params, t_span_dev):
+        """Per accepted row: its output times inside the step into ``out[j, r]``, then ``y0 <- y1``, ``ks[0] <- f1``, the cursor, done."""
+        rows, D, code, st = self._rows_call("_rows_dense_commit", ctl, y0, y0, y1, f1, *ks)
+        self._require_device(out, t_span_dev)
+        if not out.is_contiguous() or out.dtype != y0.dtype or tuple(out.shape) != (t_span_dev.numel(),) + tuple(y0.shape):
+            raise XdeError("_rows_dense_commit: the solution is a contiguous [T, *y0.shape] tensor of the state's dtype")
+        rc = self.lib.xde_rows_dense_commit(_ptr(out), _ptr_array(ks), _dbl_array(mid), len(ks), _ptr(y0), _ptr(y1), _ptr(ks[0]), _ptr(f1),
+                                            C.byref(ctl.c), C.byref(params), _ptr(t_span_dev), t_span_dev.numel(), rows, D, code, st)
+        self._check(rc, "xde_rows_dense_commit")
+
+    def _rows_scaled_norm(self, out, a, b, y0, rtol, atol):
+        """``out[r] = rms((a[r] - b[r]) / (atol + |y0[r]| * rtol))`` (``b`` None: ``a[r]``), a float64 per row.  One launch."""
+        self._require_device(out, a, b, y0)
+        for x in (a, b):
+            if x is not None and (not x.is_contiguous() or x.shape != y0.shape or x.dtype != y0.dtype):
+                raise XdeError("_rows_scaled_norm: the state operands must be contiguous tensors of one shape and dtype")
+        rows = y0.shape[0]
+        if y0.dim() < 2 or not y0.is_contiguous() or out.dtype != torch.float64 or out.numel() != rows or not out.is_contiguous():
+            raise XdeError("_rows_scaled_norm: the state is a contiguous [rows, ...] tensor and out a float64 [rows]")
+        rc = self.lib.xde_rows_scaled_norm(_ptr(out), _ptr(a), _ptr(b), _ptr(y0), float(rtol), float(atol), rows, y0.numel() // rows,
+                                           dtype_code(y0.dtype), self._stream(y0))
+        self._check(rc, "xde_rows_scaled_norm")
 
     # -- the seam between two attempts as one resident launch (include/xde_hip_seam.h) ------------------------------------------------
     # Private for the reason _interp_rows is: the public methods are the contract tests/_cpu_double.py mirrors.  Only AdaptiveRKSolver

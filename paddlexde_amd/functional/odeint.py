@@ -44,6 +44,13 @@ def odeint(
             return tuple(importer(v) for v in sol) if isinstance(sol, tuple) else importer(sol)
     if not torch.is_tensor(t_span):
         t_span = torch.as_tensor(t_span)
+    if isinstance(options, dict) and "per_sample" in options:
+        # every batch row its own step size, verdict and output cursor (solver/_rk_rows.py); False: the call below, untouched
+        options = dict(options)
+        if options.pop("per_sample"):
+            from ..solver._rk_rows import odeint_rows
+
+            return odeint_rows(func, y0, t_span, solver, rtol=rtol, atol=atol, options=options)
     if isinstance(options, dict) and "backprop" in options:
         options = dict(options)
         mode = options.pop("backprop")
