@@ -121,9 +121,12 @@ class XdeError(RuntimeError):
 _vp, _dp, _i32, _i64, _dbl = C.c_void_p, C.POINTER(C.c_double), C.c_int, C.c_int64, C.c_double
 _vpp, _params, _segs = C.POINTER(C.c_void_p), C.POINTER(XdeCtrlParams), C.POINTER(XdeSegments)
 
-# symbol -> (restype, argtypes) of every entry point include/xde_hip.h declares (tests/test_cabi.py checks the export list against the
-# header); argtypes None: not declared (the zero-argument queries)
-PROTOTYPES = {
+# header of include/ -> {symbol: (restype, argtypes)} of the entry points it declares; argtypes None: not declared (the zero-argument
+# queries).  _bind declares the tables in this order, so a library that lacks a header's kernels is refused by that header's first
+# symbol.  A new header is one more entry here and nothing else: tests/test_cabi_headers.py holds every table to its header.
+HEADERS = {}
+# the solvers' kernels, the control block and its host mirror, dense output, history, the peer-to-peer exchange, the profiler
+HEADERS["xde_hip.h"] = {
     "xde_last_error": (C.c_char_p, []),
     "xde_abi_version": (_i32, None),
     "xde_sizeof_ctrl": (_i64, None),
@@ -174,17 +177,17 @@ PROTOTYPES = {
     "xde_prof_enable": (_i32, [_i32]),
     "xde_prof_collect": (_i32, [C.POINTER(C.c_int64), _dp, _dp]),
 }
-# the entry points of include/xde_hip_backprop.h (back-propagation through the accepted steps of an adaptive solve)
-BACKPROP_PROTOTYPES = {
+# back-propagation through the accepted steps of an adaptive solve
+HEADERS["xde_hip_backprop.h"] = {
     "xde_stage_cotangent": (_i32, [_vp, _vp, _vpp, _dp, _dp, _i32, _i64, _i32, _vp]),
     "xde_dense_cotangent": (_i32, [_vpp, _vp, _dp, _i32, C.c_uint32, _i64, _i32, _vp]),
 }
-# the entry points of include/xde_hip_grid.h (the fixed-step solvers' sub-stepping); bound by load_library() after _bind
-GRID_PROTOTYPES = {
+# the fixed-step solvers' sub-stepping
+HEADERS["xde_hip_grid.h"] = {
     "xde_interp_rows": (_i32, [_vpp, C.POINTER(C.c_int), _dp, _i32, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i64, _i32, _vp]),
 }
-# the entry points of include/xde_hip_sde.h (sdeint's Euler-Maruyama, Milstein, SRK and reversible Heun steps); bound by load_library() after _bind
-SDE_PROTOTYPES = {
+# sdeint's Euler-Maruyama, Milstein, SRK and reversible Heun steps
+HEADERS["xde_hip_sde.h"] = {
     "xde_sde_em_step": (_i32, [_vp, _vp, _vp, _vp, _i64, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
     "xde_sde_em_backward": (_i32, [_vp, _vp, _vp, _i64, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
     "xde_sde_noise": (_i32, [_vp, _i64, C.c_uint64, _i64, _i32, _i32, _vp]),
@@ -204,6 +207,8 @@ SDE_PROTOTYPES = {
     "xde_sde_rheun_adjoint_stage": (_i32, [_vp] * 5 + [_i64, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
     "xde_sde_rheun_adjoint_step": (_i32, [_vp] * 7 + [_i64, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
 }
+
+
 class XdeCdePlan(C.Structure):
     """Mirror of xde_cde_plan_t (include/xde_hip_cde.h)."""
 
@@ -211,43 +216,45 @@ class XdeCdePlan(C.Structure):
         ("items", C.c_int64), ("blocks", C.c_int64)]
 
 
-# the entry points of include/xde_hip_cde.h (cdeint's control-derivative contraction and its cotangent); bound by load_library() after _bind_sde
-CDE_PROTOTYPES = {
+# cdeint's control-derivative contraction and its cotangent
+HEADERS["xde_hip_cde.h"] = {
     "xde_cde_contract": (_i32, [_vp] * 5 + [_dbl, _i32, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),
     "xde_cde_contract_backward": (_i32, [_vp] * 5 + [_dbl, _i32, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),
     "xde_cde_plan": (_i32, [_i32, _vp, _i64, _i32, _i32, _i32, C.POINTER(XdeCdePlan)]),
 }
+
+
 class XdeSeamPlan(C.Structure):
     """Mirror of xde_seam_plan_t (include/xde_hip_seam.h)."""
 
     _fields_ = [(name, C.c_int32) for name in ("blocks", "per_lane", "resident", "fits")]
 
 
-# the entry points of include/xde_hip_seam.h (error norm + controller + next first stage combine as one resident launch); bound by
-# load_library() after _bind_cde
-SEAM_PROTOTYPES = {
+# error norm + controller + next first stage combine as one resident launch
+HEADERS["xde_hip_seam.h"] = {
     "xde_seam_state_bytes": (_i64, None),
     "xde_seam_plan": (_i32, [_i64, _i32, C.POINTER(XdeSeamPlan)]),
     "xde_seam_attempt": (_i32, [_vp, _dbl] + [_vp] * 7 + [_dbl, _i64, _i32, _vp, _vp, _vp, _params, _vp, _vp, _vp, _vp, _i64, _vp]),
     "xde_seam_expired": (_i32, [_vp, C.POINTER(C.c_int64), _vp]),
 }
-# the entry points of include/xde_hip_spline.h (the natural cubic spline control: coefficient build, gather, and the two contraction
-# launches on it); bound by load_library() after _bind_seam
-SPLINE_PROTOTYPES = {
+# the natural cubic spline control: coefficient build, gather, and the two contraction launches on it
+HEADERS["xde_hip_spline.h"] = {
     "xde_spline_natural_coeffs": (_i32, [_vp] * 4 + [_i64, _i32, _i32, _i32, _vp]),
     "xde_spline_natural_gather": (_i32, [_vp] * 6 + [_i64, _i32, _i32, _i32, _i32, _vp]),
     "xde_cde_contract_natural": (_i32, [_vp] * 6 + [_dbl, _i32, _i64, _i32, _i32, _i32, _i32, _vp]),
     "xde_cde_contract_natural_backward": (_i32, [_vp] * 6 + [_dbl, _i32, _i64, _i32, _i32, _i32, _i32, _vp]),
 }
+
+
 class XdeCdeGradPlan(C.Structure):
     """Mirror of xde_cdegrad_plan_t (include/xde_hip_cdegrad.h)."""
 
     _fields_ = [(name, C.c_int32) for name in ("vec", "P", "CL", "chunks", "rows", "strided")] + [("blocks", C.c_int64)]
 
 
-# the entry points of include/xde_hip_cdegrad.h (the gradient of cdeint with respect to its control path: the control's cotangent in the
-# contraction, the transposes of the natural spline's coefficient build and gather); bound by load_library() after _bind_spline
-CDEGRAD_PROTOTYPES = {
+# the gradient of cdeint with respect to its control path: the control's cotangent in the contraction, the transposes of the natural
+# spline's coefficient build and gather
+HEADERS["xde_hip_cdegrad.h"] = {
     "xde_cde_control_grad": (_i32, [_vp] * 5 + [_dbl, _i32, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),
     "xde_cde_control_grad_natural": (_i32, [_vp] * 6 + [_dbl, _i32, _i64, _i32, _i32, _i32, _i32, _vp]),
     "xde_cde_control_grad_plan": (_i32, [_vp, _i64, _i32, _i32, _i32, C.POINTER(XdeCdeGradPlan)]),
@@ -255,15 +262,13 @@ CDEGRAD_PROTOTYPES = {
     "xde_spline_natural_coeffs_backward_workspace_bytes": (_i64, [_i64, _i32, _i32, _i32]),
     "xde_spline_natural_gather_backward": (_i32, [_vp] * 6 + [_i64, _i32, _i32, _i32, _i32, _vp]),
 }
-# the entry points of include/xde_hip_kl.h (the KL term of a latent SDE fused into the Euler-Maruyama step, and its cotangents); bound by
-# load_library() after _bind_cdegrad
-KL_PROTOTYPES = {
+# the KL term of a latent SDE fused into the Euler-Maruyama step, and its cotangents
+HEADERS["xde_hip_kl.h"] = {
     "xde_sde_kl_step": (_i32, [_vp] * 7 + [_i64, _i64, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
     "xde_sde_kl_backward": (_i32, [_vp] * 8 + [_i64, _i64, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
 }
-# the entry points of include/xde_hip_gn.h (the Euler-Maruyama step with general or scalar noise, and its cotangents); bound by
-# load_library() after _bind_kl
-GN_PROTOTYPES = {
+# the Euler-Maruyama step with general or scalar noise, and its cotangents
+HEADERS["xde_hip_gn.h"] = {
     "xde_sde_gn_step": (_i32, [_vp] * 4 + [_i64, _i64, _i64, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
     "xde_sde_gn_backward": (_i32, [_vp] * 3 + [_i64, _i64, _i64, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
 }
@@ -282,25 +287,14 @@ class XdeRowsCtl(C.Structure):
 
 
 _rows_ctl = C.POINTER(XdeRowsCtl)
-# the entry points of include/xde_hip_rows.h (per-sample adaptive stepping: every row of the batch its own step); bound by
-# load_library() after _bind_gn
-ROWS_PROTOTYPES = {
+# per-sample adaptive stepping: every row of the batch its own step
+HEADERS["xde_hip_rows.h"] = {
     "xde_rows_stage_combine": (_i32, [_vp, _vp, _vp, _vpp, _dp, _dp, _i32, _rows_ctl, _i64, _i64, _i32, _vp]),
     "xde_rows_norm_control": (_i32, [_vpp, _dp, _i32, _vp, _vp, _vp, _rows_ctl, _params, _vp, C.c_int32, _i64, _i64, _i32, _vp]),
     "xde_rows_dense_commit": (_i32, [_vp, _vpp, _dp, _i32, _vp, _vp, _vp, _vp, _rows_ctl, _params, _vp, C.c_int32, _i64, _i64, _i32, _vp]),
     "xde_rows_scaled_norm": (_i32, [_vp, _vp, _vp, _vp, _dbl, _dbl, _i64, _i64, _i32, _vp]),
 }
-SYMBOLS = tuple(PROTOTYPES)
-ROWS_SYMBOLS = tuple(ROWS_PROTOTYPES)
-KL_SYMBOLS = tuple(KL_PROTOTYPES)
-GN_SYMBOLS = tuple(GN_PROTOTYPES)
-BACKPROP_SYMBOLS = tuple(BACKPROP_PROTOTYPES)
-GRID_SYMBOLS = tuple(GRID_PROTOTYPES)
-SDE_SYMBOLS = tuple(SDE_PROTOTYPES)
-CDE_SYMBOLS = tuple(CDE_PROTOTYPES)
-SEAM_SYMBOLS = tuple(SEAM_PROTOTYPES)
-SPLINE_SYMBOLS = tuple(SPLINE_PROTOTYPES)
-CDEGRAD_SYMBOLS = tuple(CDEGRAD_PROTOTYPES)
+PROTOTYPES = {sym: proto for table in HEADERS.values() for sym, proto in table.items()}
 XDE_INTERP_MAX_ROWS = 8
 XDE_INTERP_LINEAR, XDE_INTERP_CUBIC = 0, 1
 XDE_ROW_INTERP, XDE_ROW_COPY_A, XDE_ROW_COPY_B = 0, 1, 2
@@ -354,7 +348,7 @@ _REBUILD = "rebuild it with `python -m paddlexde_amd.csrc.build --force`"
 
 
 def _declare(lib, sym):
-    proto = PROTOTYPES.get(sym) or BACKPROP_PROTOTYPES.get(sym) or GRID_PROTOTYPES.get(sym) or SDE_PROTOTYPES.get(sym) or CDE_PROTOTYPES.get(sym) or SEAM_PROTOTYPES.get(sym) or SPLINE_PROTOTYPES.get(sym) or CDEGRAD_PROTOTYPES.get(sym) or KL_PROTOTYPES.get(sym) or GN_PROTOTYPES.get(sym) or ROWS_PROTOTYPES[sym]
+    proto = PROTOTYPES[sym]
     try:
         fn = getattr(lib, sym)
     except AttributeError:
@@ -366,7 +360,8 @@ def _declare(lib, sym):
 
 
 def _bind(lib):
-    """Declare every prototype on ``lib``: first that it is the ABI this binding speaks, then the struct layouts, then the rest."""
+    """Declare every prototype on ``lib``: first that it is the ABI this binding speaks, then the struct layouts, then every entry
+    point of HEADERS in table order."""
     _declare(lib, "xde_last_error")
     version = _declare(lib, "xde_abi_version")()
     if version != ABI_VERSION:
@@ -378,61 +373,7 @@ def _bind(lib):
         raise XdeError("xde_ctrl_params_t layout mismatch between header and ctypes mirror")
     if _declare(lib, "xde_sizeof_segments")() != C.sizeof(XdeSegments):
         raise XdeError("xde_segments_t layout mismatch between header and ctypes mirror")
-    for sym in SYMBOLS + BACKPROP_SYMBOLS:
-        _declare(lib, sym)
-
-
-def _bind_grid(lib):
-    """Declare the entry points of include/xde_hip_grid.h on ``lib`` (after ``_bind``: the ABI check comes first)."""
-    for sym in GRID_SYMBOLS:
-        _declare(lib, sym)
-
-
-def _bind_sde(lib):
-    """Declare the entry points of include/xde_hip_sde.h on ``lib`` (after ``_bind``: the ABI check comes first)."""
-    for sym in SDE_SYMBOLS:
-        _declare(lib, sym)
-
-
-def _bind_cde(lib):
-    """Declare the entry points of include/xde_hip_cde.h on ``lib`` (after ``_bind``: the ABI check comes first)."""
-    for sym in CDE_SYMBOLS:
-        _declare(lib, sym)
-
-
-def _bind_seam(lib):
-    """Declare the entry points of include/xde_hip_seam.h on ``lib`` (after ``_bind``: the ABI check comes first)."""
-    for sym in SEAM_SYMBOLS:
-        _declare(lib, sym)
-
-
-def _bind_spline(lib):
-    """Declare the entry points of include/xde_hip_spline.h on ``lib`` (after ``_bind``: the ABI check comes first)."""
-    for sym in SPLINE_SYMBOLS:
-        _declare(lib, sym)
-
-
-def _bind_cdegrad(lib):
-    """Declare the entry points of include/xde_hip_cdegrad.h on ``lib`` (after ``_bind``: the ABI check comes first)."""
-    for sym in CDEGRAD_SYMBOLS:
-        _declare(lib, sym)
-
-
-def _bind_kl(lib):
-    """Declare the entry points of include/xde_hip_kl.h on ``lib`` (after ``_bind``: the ABI check comes first)."""
-    for sym in KL_SYMBOLS:
-        _declare(lib, sym)
-
-
-def _bind_gn(lib):
-    """Declare the entry points of include/xde_hip_gn.h on ``lib`` (after ``_bind``: the ABI check comes first)."""
-    for sym in GN_SYMBOLS:
-        _declare(lib, sym)
-
-
-def _bind_rows(lib):
-    """Declare the entry points of include/xde_hip_rows.h on ``lib`` (after ``_bind``: the ABI check comes first)."""
-    for sym in ROWS_SYMBOLS:
+    for sym in PROTOTYPES:
         _declare(lib, sym)
 
 
@@ -451,15 +392,6 @@ def load_library():
             )
         lib = C.CDLL(LIB_PATH)
         _bind(lib)
-        _bind_grid(lib)
-        _bind_sde(lib)
-        _bind_cde(lib)
-        _bind_seam(lib)
-        _bind_spline(lib)
-        _bind_cdegrad(lib)
-        _bind_kl(lib)
-        _bind_gn(lib)
-        _bind_rows(lib)
         _lib = lib
     return _lib
 
@@ -474,6 +406,14 @@ def dtype_code(dt: torch.dtype) -> int:
 
 def _ptr(t):
     return None if t is None else t.data_ptr()
+
+
+def _require_alike(who, what, like, tensors):
+    """Refuse a tensor of ``tensors`` (``what`` they are, to ``who``) that is not contiguous or not of ``like``'s shape and dtype; None
+    stands for a null pointer and is not checked."""
+    for x in tensors:
+        if x is not None and (not x.is_contiguous() or x.shape != like.shape or x.dtype != like.dtype):
+            raise XdeError("{}: the {} must be contiguous tensors of one shape and dtype".format(who, what))
 
 
 def _plan_dict(plan):
@@ -946,9 +886,7 @@ class HipBackend:
         for d in dsts[1:]:
             if d.stride() != dsts[0].stride() or d.shape != dsts[0].shape:
                 raise XdeError("_interp_rows: every destination row needs the same shape and strides")
-        for x in (y_a, y_b, f_a, f_b):
-            if x is not None and (not x.is_contiguous() or x.shape != y_a.shape or x.dtype != y_a.dtype):
-                raise XdeError("_interp_rows: the operands must be contiguous tensors of one shape and dtype")
+        _require_alike("_interp_rows", "operands", y_a, (y_a, y_b, f_a, f_b))
         if y_a.numel() == 0:
             return
         dt = dtype_code(y_a.dtype)
@@ -972,9 +910,7 @@ class HipBackend:
         (the zero cotangents of the reversible Heun sweep's first backward step)."""
         self._require_device(*outs, *ins)
         like = next(x for x in ins if x is not None)
-        for x in (*ins, *outs):
-            if x is not None and (not x.is_contiguous() or x.shape != like.shape or x.dtype != like.dtype):
-                raise XdeError("{}: the operands must be contiguous tensors of one shape and dtype".format(who))
+        _require_alike(who, "operands", like, (*ins, *outs))
         rc = getattr(self.lib, "xde" + who)(*[_ptr(x) for x in (*outs, *ins)], like.numel(), *scalars, dtype_code(like.dtype),
                                             self._stream(like))
         self._check(rc, "xde" + who)
@@ -1084,9 +1020,7 @@ class HipBackend:
         self._require_device(*state, *accs)
         D = like.shape[-1]
         rows = like.numel() // D if D else 0
-        for x in state:
-            if x is not None and (not x.is_contiguous() or x.shape != like.shape or x.dtype != like.dtype):
-                raise XdeError("{}: the state operands must be contiguous tensors of one shape and dtype".format(who))
+        _require_alike(who, "state operands", like, state)
         for x in accs:
             if x is not None and (not x.is_contiguous() or x.dtype != torch.float64 or x.numel() != rows):
                 raise XdeError("{}: an accumulator is a contiguous float64 tensor with one element per row".format(who))
@@ -1117,9 +1051,7 @@ class HipBackend:
         self._require_device(*state, *mats)
         if like.dim() < 1:
             raise XdeError("{}: the state needs a last axis".format(who))
-        for x in state:
-            if x is not None and (not x.is_contiguous() or x.shape != like.shape or x.dtype != like.dtype):
-                raise XdeError("{}: the state operands must be contiguous tensors of one shape and dtype".format(who))
+        _require_alike(who, "state operands", like, state)
         M = None
         for x in mats:
             if x is None:
@@ -1157,9 +1089,7 @@ class HipBackend:
         self._require_device(like, ctl.f64, ctl.i32, ctl.t_stage, *operands)
         if like.dim() < 2 or like.shape[0] != ctl.rows:
             raise XdeError("{}: the state is [rows, ...] with rows = {} (got {})".format(who, ctl.rows, tuple(like.shape)))
-        for x in operands:
-            if x is not None and (not x.is_contiguous() or x.shape != like.shape or x.dtype != like.dtype):
-                raise XdeError("{}: the state operands must be contiguous tensors of one shape and dtype".format(who))
+        _require_alike(who, "state operands", like, operands)
         return ctl.rows, like.numel() // ctl.rows, dtype_code(like.dtype), self._stream(like)
 
     def _rows_stage_combine(self, out, y0, ks, coef, ctl, *, out2=None, coef2=None):
@@ -1190,9 +1120,7 @@ class HipBackend:
     def _rows_scaled_norm(self, out, a, b, y0, rtol, atol):
         """``out[r] = rms((a[r] - b[r]) / (atol + |y0[r]| * rtol))`` (``b`` None: ``a[r]``), a float64 per row.  One launch."""
         self._require_device(out, a, b, y0)
-        for x in (a, b):
-            if x is not None and (not x.is_contiguous() or x.shape != y0.shape or x.dtype != y0.dtype):
-                raise XdeError("_rows_scaled_norm: the state operands must be contiguous tensors of one shape and dtype")
+        _require_alike("_rows_scaled_norm", "state operands", y0, (a, b))
         rows = y0.shape[0]
         if y0.dim() < 2 or not y0.is_contiguous() or out.dtype != torch.float64 or out.numel() != rows or not out.is_contiguous():
             raise XdeError("_rows_scaled_norm: the state is a contiguous [rows, ...] tensor and out a float64 [rows]")

@@ -54,7 +54,7 @@ def needs_build():
     if not os.path.exists(OUT):
         return True
     t = os.path.getmtime(OUT)
-    deps = SOURCES + HEADERS + [os.path.join(INCLUDE, h) for h in ("xde_hip.h", "xde_hip_backprop.h", "xde_hip_grid.h", "xde_hip_sde.h", "xde_hip_cde.h", "xde_hip_seam.h", "xde_hip_spline.h", "xde_hip_cdegrad.h", "xde_hip_kl.h", "xde_hip_gn.h", "xde_hip_rows.h")] + [os.path.abspath(__file__)]
+    deps = SOURCES + HEADERS + sorted(glob.glob(os.path.join(INCLUDE, "xde_hip*.h"))) + [os.path.abspath(__file__)]
     return any(os.path.getmtime(d) > t for d in deps)
 
 

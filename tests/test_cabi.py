@@ -10,23 +10,10 @@ import pytest
 from paddlexde_amd import _hip
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "xde_hip.h")
-
-
-def _declared():
-    src = open(HEADER).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(xde_[a-z_0-9]+)\s*\(", src)))
-
-
-def test_header_declares_what_python_binds():
-    assert _declared() == sorted(_hip.SYMBOLS)
 
 
 def test_library_loads_and_exports_every_symbol():
-    lib = _hip.load_library()
-    for sym in _declared():
-        assert hasattr(lib, sym), sym
+    lib = _hip.load_library()  # (binds every table of _hip.HEADERS; tests/test_cabi_headers.py holds each table to its header)
     assert lib.xde_abi_version() == _hip.ABI_VERSION == 6
 
 
@@ -38,11 +25,6 @@ def test_struct_layouts_match():
     assert _hip.XdeCtrlParams.struct_size.offset == 0 and _hip.XdeCtrlParams.abi_version.offset == 4 and _hip.XdeSegments.struct_size.offset == 0
     assert _hip.XdeCtrl.seq.offset % 8 == 0
     assert lib.xde_workspace_bytes() > 0
-    # constants mirrored from the header
-    src = open(HEADER).read()
-    for name, val in [("XDE_MAX_K", _hip.XDE_MAX_K), ("XDE_MAX_SEG", _hip.XDE_MAX_SEG), ("XDE_MAX_STAGE", _hip.XDE_MAX_STAGE),
-                      ("XDE_MIRROR_SLOTS", _hip.XDE_MIRROR_SLOTS)]:
-        assert int(re.search(r"#define {}\s+(\d+)".format(name), src).group(1)) == val
 
 
 def _fake_library(*, abi=_hip.ABI_VERSION, missing=()):
@@ -51,7 +33,7 @@ def _fake_library(*, abi=_hip.ABI_VERSION, missing=()):
     answers = {"xde_abi_version": abi, "xde_sizeof_ctrl": C.sizeof(_hip.XdeCtrl), "xde_sizeof_ctrl_params": C.sizeof(_hip.XdeCtrlParams),
                "xde_sizeof_segments": C.sizeof(_hip.XdeSegments), "xde_last_error": b""}
     return types.SimpleNamespace(**{sym: (lambda v: lambda *a: v)(answers.get(sym, 0))
-                                    for sym in _hip.SYMBOLS + _hip.BACKPROP_SYMBOLS if sym not in missing})
+                                    for sym in _hip.PROTOTYPES if sym not in missing})
 
 
 def test_bind_checks_the_abi_version_before_any_other_symbol():
@@ -186,7 +168,7 @@ def test_every_entry_point_rejects_null_arguments():
         assert msg and (name in msg or "segments" in msg), (name, msg)
     covered = set(calls) | {"xde_last_error", "xde_abi_version", "xde_sizeof_ctrl", "xde_sizeof_ctrl_params", "xde_sizeof_segments", "xde_workspace_bytes", "xde_host_free", "xde_prof_enable",
                                 "xde_p2p_mailbox_bytes", "xde_p2p_free", "xde_p2p_close", "xde_lag_grad_workspace_bytes"}
-    assert covered == set(_hip.SYMBOLS), set(_hip.SYMBOLS) ^ covered
+    assert covered == set(_hip.HEADERS["xde_hip.h"]), set(_hip.HEADERS["xde_hip.h"]) ^ covered
     assert lib.xde_host_free(None) == _hip.XDE_OK  # freeing nothing is fine
 
 
@@ -264,16 +246,13 @@ def test_a_stale_segments_mirror_gets_ebadarg():
     assert "xde_segments_t layout mismatch" in lib.xde_last_error().decode()
 
 
-def test_header_is_plain_c_and_the_cpp_example_builds(tmp_path):
-    """include/xde_hip.h is the boundary a foreign host binds: it must be valid C (and C++), and examples/cabi_dopri5.cpp — a whole
-    solve from plain C++/HIP — must build against it and the in-tree library (hipcc cross-compiles without a GPU; it RUNS in the GPU
-    suite)."""
+def test_the_cpp_example_builds(tmp_path):
+    """include/xde_hip.h is the boundary a foreign host binds (valid C and C++: tests/test_cabi_headers.py): examples/cabi_dopri5.cpp
+    — a whole solve from plain C++/HIP — must build against it and the in-tree library (hipcc cross-compiles without a GPU; it RUNS in
+    the GPU suite)."""
     import shutil
     import subprocess
 
-    for cc, lang, std in (("gcc", "c", "c99"), ("g++", "c++", "c++11")):
-        r = subprocess.run([cc, "-fsyntax-only", "-x", lang, "-std=" + std, "-Wall", "-Wextra", "-Werror", HEADER], capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     lib_dir = os.path.join(ROOT, "paddlexde_amd", "lib")
     r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O1", "-Wno-unused-value", "-I", os.path.join(ROOT, "include"),

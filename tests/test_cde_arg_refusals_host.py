@@ -17,7 +17,7 @@ with open(M.PATH) as _fh:
 
 def test_the_table_covers_the_three_headers():
     assert len(M.ENTRIES) == 13 and set(M.ENTRIES) == set(GOLDEN["cases"])
-    assert set(M.ENTRIES) == set(_hip.CDE_SYMBOLS) | set(_hip.SPLINE_SYMBOLS) | set(_hip.CDEGRAD_SYMBOLS)
+    assert set(M.ENTRIES) == set(_hip.HEADERS["xde_hip_cde.h"]) | set(_hip.HEADERS["xde_hip_spline.h"]) | set(_hip.HEADERS["xde_hip_cdegrad.h"])
     for name in M.ENTRIES:
         r = M.rules(name)
         assert {M.case_id(dict(a, **b)) for a in r.values() for b in r.values() if not set(a) & set(b)} <= set(GOLDEN["cases"][name])

@@ -2,9 +2,6 @@
 float64 Jacobian oracle (tests/_cdegrad_oracle.py), the structure of the outputs (exact zeros, the end rule, full overwrite), the
 end-to-end gradients on the double (tests/_cdegrad_e2e.py), the default path untouched, every refusal by message, the C ABI of the
 header, and the plan table."""
-import os
-import re
-import subprocess
 import types
 
 import numpy as np
@@ -28,8 +25,6 @@ from ._cde_cases import B, C, H, T, _field, inputs
 from ._cdegrad_e2e import *  # noqa: F401,F403
 from .test_srk_host import _entry
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "xde_hip_cdegrad.h")
 _U = {np.float32: 2.0**-24, np.float64: 2.0**-53}
 CS, HS = (1, 3, 5, 64), (1, 7, 33, 512)
 
@@ -324,34 +319,6 @@ def test_exports():
 # ----------------------------------------------------------------------------------------------
 # the C ABI of include/xde_hip_cdegrad.h
 # ----------------------------------------------------------------------------------------------
-def test_cdegrad_header_declares_what_python_binds_and_the_library_exports_it():
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    assert sorted(set(re.findall(r"\b(xde_[a-z_0-9]+)\s*\(", src))) == sorted(_hip.CDEGRAD_SYMBOLS) == sorted(_hip.CDEGRAD_PROTOTYPES)
-    for sym, (_, args) in _hip.CDEGRAD_PROTOTYPES.items():
-        decl = re.search(r"\b{}\s*\(([^)]*)\)".format(sym), src).group(1)
-        assert len(decl.split(",")) == len(args), sym
-    lib = _hip.load_library()
-    assert lib.xde_abi_version() == 6 == _hip.ABI_VERSION
-    for sym in _hip.CDEGRAD_SYMBOLS:
-        assert hasattr(lib, sym)
-    others = (_hip.SYMBOLS, _hip.BACKPROP_SYMBOLS, _hip.GRID_SYMBOLS, _hip.SDE_SYMBOLS, _hip.CDE_SYMBOLS, _hip.SEAM_SYMBOLS, _hip.SPLINE_SYMBOLS)
-    assert not set(_hip.CDEGRAD_SYMBOLS) & set().union(*others)
-
-
-def test_cdegrad_header_is_plain_c():
-    for cc, lang, std in (("gcc", "c", "c99"), ("g++", "c++", "c++11")):
-        r = subprocess.run([cc, "-fsyntax-only", "-x", lang, "-std=" + std, "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"),
-                            HEADER], capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr
-
-
-def test_binding_the_cdegrad_table_refuses_a_stale_library():
-    with pytest.raises(_hip.XdeError, match="xde_cde_control_grad") as e:
-        _hip._bind_cdegrad(types.SimpleNamespace())
-    assert "rebuild" in str(e.value)
-    _hip._bind_cdegrad(types.SimpleNamespace(**{s: (lambda *a: 0) for s in _hip.CDEGRAD_SYMBOLS}))
-
-
 def test_the_cdegrad_backend_methods_are_private():
     pub = {m for m in dir(_hip.HipBackend) if not m.startswith("_")}
     assert not any("control_grad" in m or "backward" in m and "spline" in m for m in pub)

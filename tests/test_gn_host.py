@@ -1,12 +1,6 @@
 """General and scalar noise without a GPU: the C ABI of include/xde_hip_gn.h (every call below is refused on the host before anything
 is enqueued, or has nothing to do), the bind, the double against the oracle, the end-to-end cases of tests/_gn_cases.py on the numpy
 double, the launches of a walk, gradcheck, and what sdeint refuses."""
-import glob
-import os
-import re
-import subprocess
-import types
-
 import numpy as np
 import pytest
 import torch
@@ -24,9 +18,6 @@ from ._gn_cases import *  # noqa: F401,F403
 from ._gn_cases import Coeffs, _Net
 from ._sde_cases import _opts, _y0
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "xde_hip_gn.h")
-
 
 @pytest.fixture
 def dev():
@@ -42,39 +33,6 @@ def dev():
 # ----------------------------------------------------------------------------------------------
 # the C ABI of include/xde_hip_gn.h
 # ----------------------------------------------------------------------------------------------
-def test_gn_header_declares_what_python_binds_and_the_library_exports_it():
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    assert sorted(set(re.findall(r"\b(xde_[a-z_0-9]+)\s*\(", src))) == sorted(_hip.GN_SYMBOLS) == sorted(_hip.GN_PROTOTYPES)
-    for sym, (_, args) in _hip.GN_PROTOTYPES.items():
-        decl = re.search(r"\b{}\s*\(([^)]*)\)".format(sym), src).group(1)
-        assert len(decl.split(",")) == len(args), sym
-    lib = _hip.load_library()
-    for sym in _hip.GN_SYMBOLS:
-        assert hasattr(lib, sym)
-    others = [getattr(_hip, n) for n in dir(_hip) if n.endswith("PROTOTYPES") and n != "GN_PROTOTYPES"]
-    assert len(others) >= 9 and not any(set(_hip.GN_PROTOTYPES) & set(o) for o in others)
-    for path in glob.glob(os.path.join(ROOT, "include", "*.h")):  # (and no other header declares them)
-        if path != HEADER:
-            assert not any(sym in open(path).read() for sym in _hip.GN_SYMBOLS), path
-
-
-def test_gn_header_is_plain_c():
-    for cc, lang, std in (("gcc", "c", "c99"), ("g++", "c++", "c++11")):
-        r = subprocess.run([cc, "-fsyntax-only", "-x", lang, "-std=" + std, "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"),
-                            HEADER], capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr
-
-
-def test_binding_the_gn_table_refuses_a_stale_library():
-    with pytest.raises(_hip.XdeError, match="xde_sde_gn_step") as e:
-        _hip._bind_gn(types.SimpleNamespace())
-    assert "rebuild" in str(e.value)
-    with pytest.raises(_hip.XdeError, match="xde_sde_gn_backward"):
-        _hip._bind_gn(types.SimpleNamespace(xde_sde_gn_step=lambda *a: 0))
-    _hip._bind_gn(types.SimpleNamespace(**{s: (lambda *a: 0) for s in _hip.GN_SYMBOLS}))
-    assert not set(_hip.GN_SYMBOLS) & (set(_hip.SDE_SYMBOLS) | set(_hip.KL_SYMBOLS))
-
-
 def test_the_gn_backend_methods_are_private():
     pub = {m for m in dir(_hip.HipBackend) if not m.startswith("_")}
     assert not any("gn" in m.split("_") or "sde" in m for m in pub)

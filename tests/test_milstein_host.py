@@ -115,7 +115,7 @@ def test_milstein_entry_points_validate_their_arguments_on_the_host():
 def test_the_library_exports_the_milstein_entry_points():
     lib = _hip.load_library()
     for sym in ("xde_sde_milstein_support", "xde_sde_milstein_support_backward", "xde_sde_milstein_step", "xde_sde_milstein_backward"):
-        assert sym in _hip.SDE_SYMBOLS and hasattr(lib, sym)
+        assert sym in _hip.HEADERS["xde_hip_sde.h"] and hasattr(lib, sym)
 
 
 def test_the_milstein_backend_methods_are_private():

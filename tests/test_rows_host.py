@@ -2,11 +2,6 @@
 anything is enqueued), the bind, the launches of an attempt, what ``per_sample`` refuses, and the end-to-end cases of
 tests/_rows_cases.py on the numpy double against the rows solved alone by the CPU oracle."""
 import ctypes as C
-import glob
-import os
-import re
-import subprocess
-import types
 
 import numpy as np
 import pytest
@@ -18,8 +13,6 @@ from paddlexde_amd.utils import _rms_norm
 from . import _rows_cases as RC
 from . import _rows_oracle as RO
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "xde_hip_rows.h")
 ATTEMPT = ["rows_stage_combine"] * 6 + ["rows_norm_control", "rows_dense_commit"]  # Dopri5: six stages, FSAL
 FIRST_STEP = ["rows_scaled_norm", "rows_scaled_norm", "rows_stage_combine", "rows_scaled_norm"]
 
@@ -53,41 +46,6 @@ def _counts(st):
 # ----------------------------------------------------------------------------------------------
 # the C ABI of include/xde_hip_rows.h
 # ----------------------------------------------------------------------------------------------
-def test_rows_header_declares_what_python_binds_and_the_library_exports_it():
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    assert sorted(set(re.findall(r"\b(xde_[a-z_0-9]+)\s*\(", src))) == sorted(_hip.ROWS_SYMBOLS) == sorted(_hip.ROWS_PROTOTYPES)
-    for sym, (_, args) in _hip.ROWS_PROTOTYPES.items():
-        decl = re.search(r"\b{}\s*\(([^)]*)\)".format(sym), src).group(1)
-        assert len(decl.split(",")) == len(args), sym
-    lib = _hip.load_library()
-    for sym in _hip.ROWS_SYMBOLS:
-        assert hasattr(lib, sym)
-    assert lib.xde_abi_version() == 6 == _hip.ABI_VERSION
-    others = [getattr(_hip, n) for n in dir(_hip) if n.endswith("PROTOTYPES") and n != "ROWS_PROTOTYPES"]
-    assert len(others) >= 10 and not any(set(_hip.ROWS_PROTOTYPES) & set(o) for o in others)
-    for path in glob.glob(os.path.join(ROOT, "include", "*.h")):  # (and no other header declares them)
-        if path != HEADER:
-            assert not any(sym in open(path).read() for sym in _hip.ROWS_SYMBOLS), path
-    planes = re.search(r"typedef struct xde_rows_ctl_t \{(.*?)\}", src, flags=re.S).group(1)
-    assert re.findall(r"(\w+);", planes) == [n for n, _ in _hip.XdeRowsCtl._fields_]
-
-
-def test_rows_header_is_plain_c():
-    for cc, lang, std in (("gcc", "c", "c99"), ("g++", "c++", "c++11")):
-        r = subprocess.run([cc, "-fsyntax-only", "-x", lang, "-std=" + std, "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"),
-                            HEADER], capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr
-
-
-def test_binding_the_rows_table_refuses_a_stale_library():
-    with pytest.raises(_hip.XdeError, match="xde_rows_stage_combine") as e:
-        _hip._bind_rows(types.SimpleNamespace())
-    assert "rebuild" in str(e.value)
-    with pytest.raises(_hip.XdeError, match="xde_rows_scaled_norm"):
-        _hip._bind_rows(types.SimpleNamespace(**{s: (lambda *a: 0) for s in _hip.ROWS_SYMBOLS if s != "xde_rows_scaled_norm"}))
-    _hip._bind_rows(types.SimpleNamespace(**{s: (lambda *a: 0) for s in _hip.ROWS_SYMBOLS}))
-
-
 def test_the_rows_backend_methods_are_private():
     pub = {m for m in dir(_hip.HipBackend) if not m.startswith("_")}
     assert not any("rows" in m.split("_") for m in pub - {"interp_rows"})

@@ -4,7 +4,6 @@ expired grid barrier does — and the C ABI's refusals (every call below is refu
 import ctypes as C
 import os
 import re
-import types
 
 import numpy as np
 import pytest
@@ -169,12 +168,8 @@ def test_geometry_is_the_error_norm_launch_s():
 # the C ABI of include/xde_hip_seam.h
 # ----------------------------------------------------------------------------------------------
 def test_header_declares_what_python_binds():
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    assert sorted(set(re.findall(r"\b(xde_[a-z_0-9]+)\s*\(", src))) == sorted(_hip.SEAM_SYMBOLS) == sorted(_hip.SEAM_PROTOTYPES)
+    """(The table against the header and the bind's refusals: tests/test_cabi_headers.py.)"""
     assert int(re.search(r"#define XDE_SEAM_CAP\s+(\d+)", open(HEADER).read()).group(1)) == 16
-    _hip._bind_seam(types.SimpleNamespace(**{s: (lambda *a: 0) for s in _hip.SEAM_SYMBOLS}))
-    with pytest.raises(_hip.XdeError, match="xde_seam_attempt"):
-        _hip._bind_seam(types.SimpleNamespace(**{s: (lambda *a: 0) for s in _hip.SEAM_SYMBOLS if s != "xde_seam_attempt"}))
 
 
 def test_seam_methods_stay_outside_the_backend_contract():

@@ -2,11 +2,6 @@
 (tests/_spline_oracle.py), the exact cases (two knots, data on a straight line), the observed data back at the knots, whole missing
 rows against the shorter series, every refusal by message, the C ABI of the header (every call is refused on the host, or — on a box
 without a GPU — runs its host half up to the launch), the launches of a cdeint walk on the natural control, and the exports."""
-import os
-import re
-import subprocess
-import types
-
 import numpy as np
 import pytest
 import torch
@@ -23,8 +18,6 @@ from ._cde_cases import B, C, H, T, _field
 from ._spline_e2e import *  # noqa: F401,F403
 from .test_srk_host import _entry
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "xde_hip_spline.h")
 _U = {np.float32: 2.0**-24, np.float64: 2.0**-53}
 
 # The double against the oracle, in units of u = the dtype's unit roundoff:
@@ -246,33 +239,6 @@ def test_exports():
 # ----------------------------------------------------------------------------------------------
 # the C ABI of include/xde_hip_spline.h
 # ----------------------------------------------------------------------------------------------
-def test_spline_header_declares_what_python_binds_and_the_library_exports_it():
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    assert sorted(set(re.findall(r"\b(xde_[a-z_0-9]+)\s*\(", src))) == sorted(_hip.SPLINE_SYMBOLS) == sorted(_hip.SPLINE_PROTOTYPES)
-    for sym, (_, args) in _hip.SPLINE_PROTOTYPES.items():
-        decl = re.search(r"\b{}\s*\(([^)]*)\)".format(sym), src).group(1)
-        assert len(decl.split(",")) == len(args), sym
-    lib = _hip.load_library()
-    assert lib.xde_abi_version() == 6 == _hip.ABI_VERSION
-    for sym in _hip.SPLINE_SYMBOLS:
-        assert hasattr(lib, sym)
-    assert not set(_hip.SPLINE_SYMBOLS) & (set(_hip.SYMBOLS) | set(_hip.CDE_SYMBOLS))
-
-
-def test_spline_header_is_plain_c():
-    for cc, lang, std in (("gcc", "c", "c99"), ("g++", "c++", "c++11")):
-        r = subprocess.run([cc, "-fsyntax-only", "-x", lang, "-std=" + std, "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"),
-                            HEADER], capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr
-
-
-def test_binding_the_spline_table_refuses_a_stale_library():
-    with pytest.raises(_hip.XdeError, match="xde_spline_natural_coeffs") as e:
-        _hip._bind_spline(types.SimpleNamespace())
-    assert "rebuild" in str(e.value)
-    _hip._bind_spline(types.SimpleNamespace(**{s: (lambda *a: 0) for s in _hip.SPLINE_SYMBOLS}))
-
-
 def test_the_spline_backend_methods_are_private():
     pub = {m for m in dir(_hip.HipBackend) if not m.startswith("_")}
     assert not any("spline" in m or "natural" in m for m in pub)

@@ -1,9 +1,6 @@
 """Sub-stepping of the fixed-step solvers (step_size / grid_constructor) on the CPU double: the end-to-end cases of
 tests/_substep_cases.py, the grid itself, the refusals, and the C ABI of xde_interp_rows without a GPU."""
 import ctypes as C
-import os
-import re
-import types
 
 import numpy as np
 import pytest
@@ -17,8 +14,6 @@ from paddlexde_amd.xde import BaseODE
 from . import _substep_oracle as SO
 from . import problems as P
 from ._substep_cases import *  # noqa: F401,F403
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture
@@ -124,17 +119,6 @@ def test_adjoint_interval_replay_is_off_with_substeps(dev):
 # ----------------------------------------------------------------------------------------------
 # the C ABI of xde_interp_rows (no GPU: every call below is refused before anything is enqueued, or has n == 0)
 # ----------------------------------------------------------------------------------------------
-def test_grid_header_declares_what_python_binds_and_the_library_exports_it():
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "xde_hip_grid.h")).read(), flags=re.S)
-    assert sorted(set(re.findall(r"\b(xde_[a-z_0-9]+)\s*\(", src))) == sorted(_hip.GRID_SYMBOLS)
-    assert int(re.search(r"#define XDE_INTERP_MAX_ROWS\s+(\d+)", src).group(1)) == _hip.XDE_INTERP_MAX_ROWS
-    for name in ("XDE_INTERP_LINEAR", "XDE_INTERP_CUBIC", "XDE_ROW_INTERP", "XDE_ROW_COPY_A", "XDE_ROW_COPY_B"):
-        assert int(re.search(r"#define {}\s+(\d+)".format(name), src).group(1)) == getattr(_hip, name)
-    lib = _hip.load_library()
-    for sym in _hip.GRID_SYMBOLS:
-        assert hasattr(lib, sym)
-
-
 def test_interp_rows_validates_its_arguments_on_the_host():
     lib = _hip.load_library()
     A, B = 0x10000, 0x20000  # (never dereferenced: every call is refused first)
@@ -155,11 +139,3 @@ def test_interp_rows_validates_its_arguments_on_the_host():
         assert rc == _hip.XDE_EBADARG, (kw, rc, msg)
         assert "xde_interp_rows" in msg, (kw, msg)
     assert call(outer=0)[0] == _hip.XDE_OK  # n == 0: nothing to launch
-
-
-def test_binding_the_grid_table_refuses_a_stale_library():
-    lib = types.SimpleNamespace()
-    with pytest.raises(_hip.XdeError, match="xde_interp_rows") as e:
-        _hip._bind_grid(lib)
-    assert "rebuild" in str(e.value)
-    _hip._bind_grid(types.SimpleNamespace(xde_interp_rows=lambda *a: 0))
