@@ -294,6 +294,12 @@ HEADERS["xde_hip_rows.h"] = {
     "xde_rows_dense_commit": (_i32, [_vp, _vpp, _dp, _i32, _vp, _vp, _vp, _vp, _rows_ctl, _params, _vp, C.c_int32, _i64, _i64, _i32, _vp]),
     "xde_rows_scaled_norm": (_i32, [_vp, _vp, _vp, _vp, _dbl, _dbl, _i64, _i64, _i32, _vp]),
 }
+# logsignature windows: the depth-2 log-ODE control of cdeint, and its cotangent
+HEADERS["xde_hip_logsig.h"] = {
+    "xde_logsig_channels": (_i64, [_i64, _i32]),
+    "xde_logsig_windows": (_i32, [_vp] * 2 + [_i64, _i64, _i64, _i64, _i32, _i32, _vp]),
+    "xde_logsig_windows_backward": (_i32, [_vp] * 3 + [_i64, _i64, _i64, _i64, _i32, _i32, _vp]),
+}
 PROTOTYPES = {sym: proto for table in HEADERS.values() for sym, proto in table.items()}
 XDE_INTERP_MAX_ROWS = 8
 XDE_INTERP_LINEAR, XDE_INTERP_CUBIC = 0, 1
@@ -414,6 +420,20 @@ def _require_alike(who, what, like, tensors):
     for x in tensors:
         if x is not None and (not x.is_contiguous() or x.shape != like.shape or x.dtype != like.dtype):
             raise XdeError("{}: the {} must be contiguous tensors of one shape and dtype".format(who, what))
+
+
+_LOGSIG_MAX_CHANNELS = 512
+
+
+def logsig_channels(channels, depth):
+    """K of include/xde_hip_logsig.h (what its channel query answers): ``channels`` at depth 1, ``channels + channels (channels - 1) / 2``
+    at depth 2; the caps are refused here, before any launch."""
+    channels, depth = int(channels), int(depth)
+    if depth not in (1, 2):
+        raise ValueError("logsignature depth {} is not built: depth 1 (increments) and depth 2 (increments and Levy areas) are".format(depth))
+    if not 1 <= channels <= _LOGSIG_MAX_CHANNELS:
+        raise ValueError("logsignature windows take 1 <= C <= {} channels, got {}".format(_LOGSIG_MAX_CHANNELS, channels))
+    return channels if depth == 1 else channels + channels * (channels - 1) // 2
 
 
 def _plan_dict(plan):
@@ -1081,6 +1101,41 @@ class HipBackend:
         if rows == 0:
             return
         self._check(self.lib.xde_sde_gn_backward(_ptr(gf), _ptr(gg), _ptr(gy1), rows, D, int(M), *tail), "xde_sde_gn_backward")
+
+    # -- logsignature windows (include/xde_hip_logsig.h) ------------------------------------------------------------------------------
+    # Private for the reason _interp_rows is.  Only interpolation.logsig_windows (and its autograd node) call these.
+    def _logsig_call(self, who, x, inc, grads, window_length, depth):
+        """The operand check the two entry points share; nothing is launched here.  ``x [.., T, C]`` and ``inc [.., W, K]`` are contiguous
+        device tensors of one floating dtype with the same leading axes, ``grads`` contiguous tensors of ``x``'s shape and dtype.
+        Returns ``(B, T, C, L, depth, dtype code, stream)``, the arguments after the pointers."""
+        self._require_device(x, inc, *grads)
+        if x.dim() < 2:
+            raise XdeError("{}: the series is [.., T, C]".format(who))
+        _require_alike(who, "series operands", x, (x, *grads))
+        T, Cn = x.shape[-2:]
+        L, depth = int(window_length), int(depth)
+        K = logsig_channels(Cn, depth)
+        if L < 1 or T < 2:
+            raise XdeError("{}: window_length >= 1 and T >= 2 (got {} and {})".format(who, L, T))
+        W = -(-(T - 1) // L)
+        if not inc.is_contiguous() or inc.dtype != x.dtype or tuple(inc.shape) != tuple(x.shape[:-2]) + (W, K):
+            raise XdeError("{}: the windows are a contiguous tensor of shape {} and dtype {}, got {} {}".format(
+                who, tuple(x.shape[:-2]) + (W, K), x.dtype, tuple(inc.shape), inc.dtype))
+        return x.numel() // (T * Cn), T, Cn, L, depth, dtype_code(x.dtype), self._stream(x)
+
+    def _logsig_windows(self, out, x, window_length, depth):
+        """``out [.., W, K]`` <- the logsignatures of the windows of ``window_length`` steps of ``x [.., T, C]``.  One launch."""
+        tail = self._logsig_call("_logsig_windows", x, out, (), window_length, depth)
+        if tail[0] == 0:
+            return
+        self._check(self.lib.xde_logsig_windows(_ptr(out), _ptr(x), *tail), "xde_logsig_windows")
+
+    def _logsig_windows_backward(self, gx, gout, x, window_length, depth):
+        """``gx [.., T, C]`` <- the cotangent of ``x`` from ``gout [.., W, K]``, that of ``_logsig_windows``' output.  One launch."""
+        tail = self._logsig_call("_logsig_windows_backward", x, gout, (gx,), window_length, depth)
+        if tail[0] == 0:
+            return
+        self._check(self.lib.xde_logsig_windows_backward(_ptr(gx), _ptr(gout), _ptr(x), *tail), "xde_logsig_windows_backward")
 
     # -- per-sample adaptive stepping (include/xde_hip_rows.h) ------------------------------------------------------------------------
     # Private for the reason _interp_rows is.  Only solver/_rk_rows.py calls these.  ``ctl`` is a ``RowsCtl``.

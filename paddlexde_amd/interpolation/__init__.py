@@ -11,12 +11,16 @@ the reference's own tests for these classes (tests/interpolation/test_interpolat
 ``NaturalCubicSpline`` is this project's own (the reference has none): the C2 natural cubic spline through the observed entries of a
 series on arbitrary strictly increasing knots, NaN meaning "not observed" — the control path of ``cdeint`` for irregularly sampled,
 partly observed data (include/xde_hip_spline.h states the path op for op).
+
+``logsig_windows`` / ``logsig_path`` are the log-ODE method's transform of a long series (include/xde_hip_logsig.h): windows of
+``window_length`` steps replaced by their depth-1 or depth-2 logsignatures, the path to hand to one of the classes above.
 """
 import torch
 
 from .. import _hip
 
-__all__ = ["LinearInterpolation", "CubicHermiteSpline", "BezierSpline", "NaturalCubicSpline"]
+__all__ = ["LinearInterpolation", "CubicHermiteSpline", "BezierSpline", "NaturalCubicSpline", "logsignature_channels", "logsig_windows",
+           "logsig_path", "window_times"]
 
 
 def _gather_buffers(rows, t):
@@ -200,3 +204,88 @@ class NaturalCubicSpline(InterpolationBase):
         tq, val, der = _gather_buffers(self._series, t)
         self._backend._spline_natural_gather(val, der, self._series, self._coef, self._t, tq)
         return val, der
+
+
+class LogsigWindowsFn(torch.autograd.Function):
+    """``out = xde_logsig_windows(x)`` with the gradient to ``x [B.., T, C]``: one xde_logsig_windows_backward launch
+    (include/xde_hip_logsig.h).  The forward saves the series only; an absent cotangent stays absent."""
+
+    @staticmethod
+    def forward(ctx, x, window_length, depth):
+        T, C = x.shape[-2:]
+        out = torch.empty(tuple(x.shape[:-2]) + (-(-(T - 1) // window_length), _hip.logsig_channels(C, depth)), dtype=x.dtype, device=x.device)
+        _hip.get_backend()._logsig_windows(out, x, window_length, depth)
+        ctx.save_for_backward(x)
+        ctx.plan = (window_length, depth)
+        ctx.set_materialize_grads(False)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        if gout is None:
+            return None, None, None
+        (x,) = ctx.saved_tensors
+        gx = torch.empty_like(x)
+        _hip.get_backend()._logsig_windows_backward(gx, gout.contiguous(), x, *ctx.plan)
+        return gx, None, None
+
+
+def logsignature_channels(channels, depth=2):
+    """Channels of a logsignature of ``channels`` channels: ``channels`` at depth 1, ``channels (channels + 1) / 2`` at depth 2."""
+    return _hip.logsig_channels(channels, depth)
+
+
+def _windows_args(series, depth, window_length):
+    """What logsig_windows refuses, before the first launch; returns the series (contiguous) and the window length."""
+    be = _hip.get_backend()
+    if not torch.is_tensor(series) or not series.is_floating_point() or series.dtype not in (torch.float32, torch.float64):
+        raise TypeError("logsig_windows: the series must be a float32 or float64 tensor, got {}".format(
+            series.dtype if torch.is_tensor(series) else type(series).__name__))
+    if series.dim() < 2:
+        raise ValueError("logsig_windows: the series is [..., T, C], got shape {}".format(tuple(series.shape)))
+    if isinstance(window_length, bool) or int(window_length) != window_length or int(window_length) < 1:
+        raise ValueError("logsig_windows: window_length must be an integer >= 1, got {!r}".format(window_length))
+    if isinstance(depth, bool) or int(depth) != depth:
+        raise ValueError("logsig_windows: depth must be 1 or 2, got {!r}".format(depth))
+    _hip.logsig_channels(series.shape[-1], depth)  # (depth and the channel cap)
+    if series.shape[-2] < 2:
+        raise ValueError("logsig_windows: the series needs at least 2 time points (T >= 2), got T = {}".format(series.shape[-2]))
+    be.require_device(series)
+    return series.contiguous(), int(window_length)
+
+
+def logsig_windows(series, depth=2, window_length=1):
+    """The logsignatures of the windows of ``window_length`` steps of ``series [..., T, C]``: ``[..., W, K]`` with
+    ``W = ceil((T - 1) / window_length)`` (the last window may be shorter) and ``K = logsignature_channels(C, depth)`` — per window its
+    increment (the first ``C`` channels) and, at depth 2, its Levy areas ``A_ij = 1/2 * sum_k (u_k[i] D_k[j] - u_k[j] D_k[i])`` for the pairs
+    ``i < j`` in lexicographic order (``u_k`` the offset of point k from the window's first point, ``D_k`` step k).  One launch
+    (xde_logsig_windows), accumulated in float64 in a fixed order; differentiable with respect to the series through one launch
+    (xde_logsig_windows_backward).  A NaN entry poisons its own windows only: fill unobserved entries first."""
+    series, window_length = _windows_args(series, depth, window_length)
+    return LogsigWindowsFn.apply(series, window_length, int(depth))
+
+
+def logsig_path(series, depth=2, window_length=1):
+    """The control path of the log-ODE method: ``[..., W + 1, K]``, a zero row followed by the cumulative sum of ``logsig_windows`` along
+    the window axis.  Hand it to ``LinearInterpolation(path, differentiable=...)`` (its derivative on window w is that window's
+    logsignature over the window's length) or ``NaturalCubicSpline(path, t=window_times(t, window_length))``, and that to ``cdeint``
+    with ``step_size`` sub-stepping inside the windows.
+
+    THE VECTOR FIELD the path is contracted with has K columns: ``func(t, z)`` returns ``[..., H, K]``.  Its first C columns are the
+    fields ``V_c(z)`` of the CDE ``dz = sum_c V_c(z) dX_c`` on the original series.  Column ``pair(i, j)`` (``C + i (2 C - i - 1) / 2 +
+    (j - i - 1)``, ``i < j``) is the Lie bracket ``[V_i, V_j](z) = DV_j(z) V_i(z) - DV_i(z) V_j(z)``; for linear fields
+    ``V_c(z) = A_c z`` that is ``(A_j A_i - A_i A_j) z``.  With the opposite sign the depth-2 solve is worse than the depth-1 one."""
+    inc = logsig_windows(series, depth, window_length)
+    return torch.cat([torch.zeros_like(inc[..., :1, :]), torch.cumsum(inc, dim=-2)], dim=-2)
+
+
+def window_times(t, window_length):
+    """The knots of the windows of ``window_length`` steps over the times ``t [T]``: ``t[0], t[L], t[2 L], ..., t[T - 1]``."""
+    t = torch.as_tensor(t).reshape(-1)
+    if isinstance(window_length, bool) or int(window_length) != window_length or int(window_length) < 1:
+        raise ValueError("window_times: window_length must be an integer >= 1, got {!r}".format(window_length))
+    if t.numel() < 2:
+        raise ValueError("window_times: t needs at least 2 time points")
+    idx = list(range(0, t.numel() - 1, int(window_length))) + [t.numel() - 1]
+    return t[torch.as_tensor(idx, device=t.device)]
