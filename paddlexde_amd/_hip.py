@@ -272,6 +272,12 @@ HEADERS["xde_hip_gn.h"] = {
     "xde_sde_gn_step": (_i32, [_vp] * 4 + [_i64, _i64, _i64, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
     "xde_sde_gn_backward": (_i32, [_vp] * 3 + [_i64, _i64, _i64, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
 }
+# ddeint_steps: the delayed states of one stage from the Hermite tape of the solution, and the fan of their cotangent into its nodes
+HEADERS["xde_hip_dde.h"] = {
+    "xde_dde_tape_gather": (_i32, [_vp, _vp, _vpp, C.POINTER(C.c_int64), _dp, _dp, _i64, _i64, _i32, _i32, _i32, _i32, _vp]),
+    "xde_dde_tape_gather_backward": (_i32, [_vpp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _dp, _i32, _vp, _i64, _i64, _i32, _i32, _i32,
+                                            _vp]),
+}
 
 
 class XdeRowsCtl(C.Structure):
@@ -305,6 +311,7 @@ XDE_INTERP_MAX_ROWS = 8
 XDE_INTERP_LINEAR, XDE_INTERP_CUBIC = 0, 1
 XDE_ROW_INTERP, XDE_ROW_COPY_A, XDE_ROW_COPY_B = 0, 1, 2
 XDE_NOISE_NORMAL, XDE_NOISE_BITS = 0, 1
+XDE_DDE_MAX_LAGS = 16  # delays of one xde_dde_tape_gather launch (include/xde_hip_dde.h)
 
 
 class RowsCtl:
@@ -1101,6 +1108,70 @@ class HipBackend:
         if rows == 0:
             return
         self._check(self.lib.xde_sde_gn_backward(_ptr(gf), _ptr(gg), _ptr(gy1), rows, D, int(M), *tail), "xde_sde_gn_backward")
+
+    # -- the Hermite tape of ddeint_steps (include/xde_hip_dde.h) ---------------------------------------------------------------------
+    # Private for the reason _interp_rows is.  Only xde/steps_dde.py's autograd node (solver/_autograd.py: DdeTapeGatherFn) calls these.
+    def _dde_rows(self, who, x, rows, D, what):
+        """The row stride (elements) of ``x``, a ``[rows, D]`` device tensor of unit element stride whose rows do not overlap."""
+        if x.dim() != 2 or tuple(x.shape) != (rows, D) or (D > 1 and x.stride(1) != 1) or (rows > 1 and x.stride(0) < D):
+            raise XdeError("{}: {} must be a [rows, D] = [{}, {}] tensor of unit element stride and a row stride >= D, got shape {} strides {}".format(
+                who, what, rows, D, tuple(x.shape), x.stride()))
+        return int(x.stride(0)) if rows > 1 else D
+
+    def _dde_tape_gather(self, out, dtau, srcs, w, wd=None):
+        """``out [rows, L, D]`` (and ``dtau``, unless None) <- the Hermite interpolant of every delay ``j < L`` of one stage:
+        ``srcs[4j .. 4j + 3]`` are the ``[rows, D]`` end states and derivatives ``ya, fa, yb, fb`` of the delay's interval (tape nodes, or
+        strided rows of a ``[rows, Th, D]`` history), ``w`` / ``wd`` the ``4L`` value / delay-derivative weights (host floats).  One
+        launch per ``XDE_DDE_MAX_LAGS`` delays."""
+        who = "_dde_tape_gather"
+        self._require_device(out, dtau, *srcs)
+        if out.dim() != 3 or not out.is_contiguous():
+            raise XdeError("{}: out must be a contiguous [rows, L, D] tensor".format(who))
+        rows, L, D = out.shape
+        if (dtau is None) != (wd is None):
+            raise XdeError("{}: dtau and wd are given together or not at all".format(who))
+        _require_alike(who, "outputs", out, (dtau,))
+        if L < 1 or len(srcs) != 4 * L or len(w) != 4 * L or (wd is not None and len(wd) != 4 * L):
+            raise XdeError("{}: {} delays take {} operands and weights (got {} and {})".format(who, L, 4 * L, len(srcs), len(w)))
+        if any(x.dtype != out.dtype for x in srcs):
+            raise XdeError("{}: every operand must have the outputs' dtype {}".format(who, out.dtype))
+        strides = [self._dde_rows(who, x, rows, D, "operand {}".format(i)) for i, x in enumerate(srcs)]
+        if rows == 0 or D == 0:
+            return
+        code, stream = dtype_code(out.dtype), self._stream(out)
+        for j0 in range(0, L, XDE_DDE_MAX_LAGS):
+            n = min(XDE_DDE_MAX_LAGS, L - j0)
+            sl = slice(4 * j0, 4 * (j0 + n))
+            rc = self.lib.xde_dde_tape_gather(out.data_ptr(), _ptr(dtau), _ptr_array(srcs[sl]), (C.c_int64 * (4 * n))(*strides[sl]),
+                                              _dbl_array(w[sl]), _dbl_array(wd[sl]) if wd is not None else None, rows, D, n, j0, L, code,
+                                              stream)
+            self._check(rc, "xde_dde_tape_gather")
+
+    def _dde_tape_gather_backward(self, gouts, terms, g, j0=0):
+        """``gouts[q]`` (contiguous ``[rows, D]``) <- the sum over ``terms[q] = [(lag, weight), ...]``, in that order, of
+        ``g[:, j0 + lag, :] * weight``: the cotangents of the distinct node tensors the delays ``j0 + lag`` of a gather read, from
+        ``g [rows, L, D]``, that of its ``out``.  One launch (at most ``4 XDE_DDE_MAX_LAGS`` outputs and terms)."""
+        who = "_dde_tape_gather_backward"
+        self._require_device(g, *gouts)
+        if g.dim() != 3 or not g.is_contiguous():
+            raise XdeError("{}: g must be a contiguous [rows, L, D] tensor".format(who))
+        rows, L, D = g.shape
+        nq = len(gouts)
+        if nq < 1 or len(terms) != nq or any(len(ts) < 1 for ts in terms):
+            raise XdeError("{}: every output takes a list of at least one (lag, weight) term".format(who))
+        for o in gouts:
+            if not o.is_contiguous() or tuple(o.shape) != (rows, D) or o.dtype != g.dtype:
+                raise XdeError("{}: every output must be a contiguous [rows, D] tensor of g's dtype".format(who))
+        if rows == 0 or D == 0:
+            return
+        first, lag, wt = [0], [], []
+        for ts in terms:
+            lag += [int(j) for j, _ in ts]
+            wt += [float(x) for _, x in ts]
+            first.append(len(lag))
+        rc = self.lib.xde_dde_tape_gather_backward(_ptr_array(gouts), (C.c_int32 * (nq + 1))(*first), (C.c_int32 * len(lag))(*lag),
+                                                   _dbl_array(wt), nq, g.data_ptr(), rows, D, int(j0), L, dtype_code(g.dtype), self._stream(g))
+        self._check(rc, "xde_dde_tape_gather_backward")
 
     # -- logsignature windows (include/xde_hip_logsig.h) ------------------------------------------------------------------------------
     # Private for the reason _interp_rows is.  Only interpolation.logsig_windows (and its autograd node) call these.

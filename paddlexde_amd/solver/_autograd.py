@@ -1,4 +1,4 @@
-"""Autograd nodes around the step kernels (xde_stage_combine, xde_interp_rows, xde_sde_em_step, xde_sde_milstein_step, xde_sde_srk_*, xde_sde_rheun_*, xde_sde_kl_*, xde_sde_gn_*) for discretise-then-optimise training.
+"""Autograd nodes around the step kernels (xde_stage_combine, xde_interp_rows, xde_sde_em_step, xde_sde_milstein_step, xde_sde_srk_*, xde_sde_rheun_*, xde_sde_kl_*, xde_sde_gn_*, xde_dde_tape_gather) for discretise-then-optimise training.
 
 The reference trains by back-propagating through its eager solver ops (example/ode_demo.py:51-53:
 ``pred_y = odeint(func, batch_y0, t_span, solver=RK4); loss.backward()``).  Here the forward is one combine launch
@@ -363,3 +363,63 @@ class SdeKlAccFn(torch.autograd.Function):
         if any(o is not None for o in (gf, gg, gh)):
             ctx.backend._sde_kl_backward(gf, gg, gh, None, gacc, f, g, h, ctx.dt, 0.0, 0, 0)
         return (None, None, gf, gg, gh, gacc if needs[3] else None)
+
+
+class DdeTapeGatherFn(torch.autograd.Function):
+    """The delayed states of ONE stage of ddeint_steps, ``y_lags[.., j, :] = H(s - lags[j])`` with H the cubic Hermite interpolant of
+    the tape (``HipBackend._dde_tape_gather``: one launch per ``XDE_DDE_MAX_LAGS`` delays), as an autograd node.  ``plan`` is the
+    stage's host plan (xde/steps_dde.py: ``StagePlan``): per delay the four operands of its interval — a history row (a plain tensor,
+    no gradient, unless ``plan.dep`` says that the row is itself a function of one of ``nodes``: the forward-difference derivative of the
+    history's last two samples moves with tape node 0's state, scaled by ``1 / dt``) or the index of one of ``nodes``, the distinct tape
+    tensors the stage reads — and the float64 weights.  The node saves
+    the plan, and ``dtau`` (the derivative of every value with respect to its delay) only when ``lags`` requires grad.  Backward: one
+    ``_dde_tape_gather_backward`` launch per tile of delays writes the cotangents of the wanted nodes (a node hit by two tiles is
+    summed in tile order), and ``grad_lags = lag_grad(g, dtau)``; an unwanted cotangent stays None."""
+
+    @staticmethod
+    def forward(ctx, backend, plan, lags, *nodes):
+        rows, L, D = plan.rows, plan.L, plan.D
+        flat = [x.detach().view(rows, D) for x in nodes]
+        srcs = [flat[s] if isinstance(s, int) else s for s in plan.src]
+        like = nodes[0] if nodes else plan.like
+        out = torch.empty(rows, L, D, dtype=like.dtype, device=like.device)
+        want_tau = lags is not None and lags.requires_grad
+        dtau = torch.empty_like(out) if want_tau else None
+        backend._dde_tape_gather(out, dtau, srcs, plan.w, plan.wd if want_tau else None)
+        ctx.backend, ctx.plan = backend, plan
+        ctx.shapes = [tuple(x.shape) for x in nodes]
+        if want_tau:
+            ctx.save_for_backward(dtau)
+        return out.view(plan.lead + (L, D))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        plan, be = ctx.plan, ctx.backend
+        rows, L, D = plan.rows, plan.L, plan.D
+        g = _cotangent(g).view(rows, L, D)
+        needs = ctx.needs_input_grad[3:]
+        grads = [None] * len(needs)
+        for j0 in range(0, L, _hip.XDE_DDE_MAX_LAGS):
+            terms = {}  # node -> its (lag within the tile, weight) terms, in delay and operand order
+            for j in range(j0, min(j0 + _hip.XDE_DDE_MAX_LAGS, L)):
+                for s in range(4):
+                    n, scale = plan.src[4 * j + s], 1.0
+                    if not isinstance(n, int):  # a history operand: no gradient, unless it is itself a function of a tape tensor
+                        if plan.dep[4 * j + s] is None:
+                            continue
+                        n, scale = plan.dep[4 * j + s]
+                    if needs[n]:
+                        terms.setdefault(n, []).append((j - j0, plan.w[4 * j + s] * scale))
+            if not terms:
+                continue
+            order = sorted(terms)
+            outs = [torch.empty(rows, D, dtype=g.dtype, device=g.device) for _ in order]
+            be._dde_tape_gather_backward(outs, [terms[n] for n in order], g, j0)
+            for n, o in zip(order, outs):
+                grads[n] = o if grads[n] is None else grads[n] + o
+        g_lags = None
+        if ctx.needs_input_grad[2]:
+            (dtau,) = ctx.saved_tensors
+            g_lags = be.lag_grad(g, dtau).reshape(plan.lags_shape).to(device=plan.lags_device, dtype=plan.lags_dtype)
+        return (None, None, g_lags) + tuple(None if o is None else o.view(shape) for o, shape in zip(grads, ctx.shapes))
