@@ -267,6 +267,12 @@ HEADERS["xde_hip_kl.h"] = {
     "xde_sde_kl_step": (_i32, [_vp] * 7 + [_i64, _i64, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
     "xde_sde_kl_backward": (_i32, [_vp] * 8 + [_i64, _i64, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
 }
+# per-sample output times of a joint adaptive solve: every row's own queries from the dense output of a step, and their cotangent
+# (the newest table; it sits here because the order of the tables after it is pinned by their own tests)
+HEADERS["xde_hip_teval.h"] = {
+    "xde_teval_dense": (_i32, [_vp, _vp, _vp, _vpp, _dp, _i32, _vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _i32, _i32, _i64, _i64, _i64, _i32, _vp]),
+    "xde_teval_cotangent": (_i32, [_vpp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _i32, _i32, C.c_uint32, _i64, _i64, _i64, _i32, _vp]),
+}
 # the Euler-Maruyama step with general or scalar noise, and its cotangents
 HEADERS["xde_hip_gn.h"] = {
     "xde_sde_gn_step": (_i32, [_vp] * 4 + [_i64, _i64, _i64, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
@@ -1253,6 +1259,41 @@ class HipBackend:
         rc = self.lib.xde_rows_scaled_norm(_ptr(out), _ptr(a), _ptr(b), _ptr(y0), float(rtol), float(atol), rows, y0.numel() // rows,
                                            dtype_code(y0.dtype), self._stream(y0))
         self._check(rc, "xde_rows_scaled_norm")
+
+    # -- per-sample output times of a joint solve (include/xde_hip_teval.h) --------------------------------------------------------------
+    # Private for the reason _interp_rows is.  Only solver/_rk_teval.py calls these.  ``tq`` is float64 ``[rows, Q]`` (time-dtype values),
+    # ``cnt`` int32 ``[rows]``; the step ``(t0, t1]`` and its ``dt`` are host floats.
+    def _teval_call(self, who, big, tq, cnt, like, operands):
+        """The operand check the two entry points share; nothing is launched here.  Returns ``(rows, D, Q, dtype code, stream)``."""
+        self._require_device(big, tq, cnt, like, *operands)
+        if like.dim() < 2 or not like.is_contiguous():
+            raise XdeError("{}: the state is a contiguous [rows, ...] tensor (got {})".format(who, tuple(like.shape)))
+        rows = like.shape[0]
+        _require_alike(who, "state operands", like, operands)
+        if tq.dim() != 2 or tq.shape[0] != rows or tq.dtype != torch.float64 or not tq.is_contiguous():
+            raise XdeError("{}: tq is a contiguous float64 [rows, Q] tensor with rows = {}".format(who, rows))
+        Q = tq.shape[1]
+        if cnt.dtype != torch.int32 or tuple(cnt.shape) != (rows,) or not cnt.is_contiguous():
+            raise XdeError("{}: cnt is a contiguous int32 [rows] tensor".format(who))
+        if not big.is_contiguous() or big.dtype != like.dtype or tuple(big.shape) != (Q,) + tuple(like.shape):
+            raise XdeError("{}: out / g is a contiguous [Q, *state.shape] tensor of the state's dtype".format(who))
+        return rows, like.numel() // rows, Q, dtype_code(like.dtype), self._stream(like)
+
+    def _teval_dense(self, out, tq, cnt, ks, mid, y0, y1, f0, f1, t0, t1, dt, direction, time_dtype):
+        """``out[q, r]`` <- row r of the step's dense output at ``tq[r, q]``, for the queries of row r inside ``(t0, t1]``.  One launch."""
+        rows, D, Q, code, st = self._teval_call("_teval_dense", out, tq, cnt, y0, [y1, f0, f1] + list(ks))
+        rc = self.lib.xde_teval_dense(_ptr(out), _ptr(tq), _ptr(cnt), _ptr_array(ks), _dbl_array(mid), len(ks), _ptr(y0), _ptr(y1), _ptr(f0),
+                                      _ptr(f1), float(t0), float(t1), float(dt), int(direction), int(time_dtype), rows, D, Q, code, st)
+        self._check(rc, "xde_teval_dense")
+
+    def _teval_cotangent(self, outs, g, tq, cnt, t0, t1, dt, direction, time_dtype, acc_mask=0):
+        """outs = [y0, y1, y_mid, f0, f1] cotangents (None: not written) <- the cotangents ``g[q, r]`` of the queries inside ``(t0, t1]``;
+        bit k of ``acc_mask``: outs[k] accumulates.  One launch."""
+        like = next(o for o in outs if o is not None)
+        rows, D, Q, code, st = self._teval_call("_teval_cotangent", g, tq, cnt, like, [o for o in outs if o is not None])
+        rc = self.lib.xde_teval_cotangent((C.c_void_p * 5)(*[_ptr(o) for o in outs]), _ptr(g), _ptr(tq), _ptr(cnt), float(t0), float(t1),
+                                          float(dt), int(direction), int(time_dtype), int(acc_mask) & 0x1F, rows, D, Q, code, st)
+        self._check(rc, "xde_teval_cotangent")
 
     # -- the seam between two attempts as one resident launch (include/xde_hip_seam.h) ------------------------------------------------
     # Private for the reason _interp_rows is: the public methods are the contract tests/_cpu_double.py mirrors.  Only AdaptiveRKSolver

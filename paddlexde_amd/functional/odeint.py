@@ -51,6 +51,12 @@ def odeint(
             from ..solver._rk_rows import odeint_rows
 
             return odeint_rows(func, y0, t_span, solver, rtol=rtol, atol=atol, options=options)
+    if isinstance(options, dict) and "t_eval" in options:
+        # every batch row its own output times, read from the dense output of one joint solve over t_span's two ends, and trained
+        # through its accepted steps (solver/_rk_teval.py)
+        from ..solver._rk_teval import odeint_teval
+
+        return odeint_teval(func, y0, t_span, solver, rtol=rtol, atol=atol, options=options)
     if isinstance(options, dict) and "backprop" in options:
         options = dict(options)
         mode = options.pop("backprop")

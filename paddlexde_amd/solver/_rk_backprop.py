@@ -23,6 +23,10 @@ The first step's ``k_0 = func(t_0, y0)`` gets the last VJP; the rows at the star
 Each step's retained tensors are released as soon as its backward is done.  S + 1 element-wise launches per accepted step (+1 for a
 step that covers an output time; Dopri8's stage 0 takes two launches then: 17 operands > XDE_BP_MAX_X).
 
+Two methods are seams a subclass overrides (solver/_rk_teval.py, per-sample output times): ``_record`` — what the hook keeps of an
+accepted step — and ``_step_cotangents`` — how the cotangents of what a step put out become those of the quartic's operands (step 2);
+``_start_terms`` are the cotangents that reach ``y0`` directly.  This class's own versions are the joint route, launch for launch.
+
 Deviation from the reference: its first step size comes from ``select_initial_step``, which is not ``no_grad`` and
 so carries a graph to y0 and func; here it is held constant like every other step size.
 """
@@ -68,19 +72,60 @@ class StepsRun:
         if self._user_hook is not None:
             self._user_hook(index, y0, y1, ks, c)
         if c.accept and c.status == _hip.STATUS_OK:
-            self.steps.append(_Step(float(c.t0), float(c.t1), float(c.dt_last), int(c.out_begin), int(c.out_end), y0, ks[0]))
+            rec = self._record(c, y0, y1, ks)
+            if rec is not None:
+                self.steps.append(rec)
             self.y_last = y1 if self.probe is not None else None
+
+    # -- the two seams a subclass overrides (solver/_rk_teval.py): what an accepted step leaves behind, and how the cotangents of what
+    # it put out become those of the quartic's operands --------------------------------------------------------------------------
+    def _record(self, c, y0, y1, ks):
+        """What the backward keeps of the accepted step the hook has just seen (None: nothing)."""
+        return _Step(float(c.t0), float(c.t1), float(c.dt_last), int(c.out_begin), int(c.out_end), y0, ks[0])
+
+    def _step_cotangents(self, st, g, lam):
+        """The cotangents ``g`` of what step ``st`` put out, as those of the quartic's operands: ``lam += y1bar`` in place, and
+        ``(y0bar, ymbar, f0bar, f1bar, dts)`` returned; None for a step that put out nothing (no launch)."""
+        if st.oe <= st.ob:
+            return None
+        TT, Y = self.tdtype, np_dtype(self.sdtype)
+        ts = self.t_host
+        t0, t1 = TT(st.t0), TT(st.t1)
+        dts = float(Y(TT(st.dt)))  # `dt.astype(y0.dtype)` of the dense kernel
+        w = []
+        for r in range(st.ob, st.oe):
+            x = float(Y((TT(ts[r]) - t0) / (t1 - t0)))
+            p0, p1, pm, q0, q1 = quartic_weights(x, dts)
+            w.append((p0 + pm, p1, pm, q0, q1))  # (y_mid = y0 + ...: its cotangent reaches y0 as well)
+        y0bar, ymbar, f0bar, f1bar = (torch.empty_like(lam) for _ in range(4))
+        self.be.dense_cotangent([y0bar, lam, ymbar, f0bar, f1bar], g[st.ob : st.oe], w, acc_mask=0b10)
+        return y0bar, ymbar, f0bar, f1bar, dts
+
+    def _start_terms(self, g):
+        """The cotangents that reach ``y0`` directly, as ``[(tensor, 1.0)]``: the output rows at the start time."""
+        ts = self.t_host
+        d = 1.0 if len(ts) < 2 or ts[-1] >= ts[0] else -1.0
+        e = 1
+        while e < len(ts) and d * ts[e] <= d * ts[0]:
+            e += 1
+        return [(g[r].view(self.shape), 1.0) for r in range(min(e, g.shape[0]))]
+
+    def _adopt(self, s):
+        """What the backward needs of the solver ``s`` (known once it is constructed: the hook may use it during the solve)."""
+        self.be = s.backend
+        self.tdtype = np_dtype(s.dtype)
+        self.tcode = _hip.dtype_code(s.dtype)
+        self.t_host = t_span_to_host(self.t_span, self.tdtype)
+        (self.S, self.stage_plan, self.fsal, self.sol_plan, self.presum, self.mid_plan) = (
+            s._n_stage, s._stage_plan, s._fsal, s._sol_plan, s._presum, s._mid_plan)
 
     def forward(self, y0):
         xde = self._BaseODE(self.func, y0=y0, t_span=self.t_span)
         s = self.solver_cls(xde=xde, y0=xde.y0, rtol=self.rtol, atol=self.atol, pipeline="sync", _step_hook=self._hook,
                             **self.options)
+        self._adopt(s)
         solution = s.integrate(self.t_span)
-        self.be = s.backend
         self.shape, self.sdtype, self.device = tuple(solution.shape[1:]), solution.dtype, solution.device
-        self.tdtype = np_dtype(s.dtype)
-        self.t_host = t_span_to_host(self.t_span, self.tdtype)
-        (self.S, self.stage_plan, self.fsal, self.sol_plan, self.presum) = (s._n_stage, s._stage_plan, s._fsal, s._sol_plan, s._presum)
         tab = s.tableau
         self.alpha = [float(a) for a in tab.alpha]
         self.beta = [[float(b) for b in row] for row in tab.beta]
@@ -170,14 +215,14 @@ class StepsRun:
                 pg[j] = g if pg[j] is None else pg[j] + g
 
     def backward(self, grad_solution):
-        be, S, shape = self.be, self.S, self.shape
+        S, shape = self.S, self.shape
         T_rows = grad_solution.shape[0]
         g = as_operand(grad_solution.detach().to(self.sdtype).reshape(T_rows, -1))
         like = torch.empty(shape, dtype=self.sdtype, device=self.device)
         lam = torch.zeros_like(like)
         carry = None
         pg = [None] * len(self.params)
-        TT, Y = self.tdtype, np_dtype(self.sdtype)
+        TT = self.tdtype
         ts = self.t_host
         for n in range(len(self.steps) - 1, -1, -1):
             st = self.steps[n]
@@ -185,17 +230,10 @@ class StepsRun:
             leaves, kg, ks, times = self._recompute(st)
             if self.probe is not None:
                 self._probe(n, ks, leaves, times)
-            dense = st.oe > st.ob
+            cot = self._step_cotangents(st, g, lam)
+            dense = cot is not None
             if dense:
-                t0, t1 = TT(st.t0), TT(st.t1)
-                dts = float(Y(TT(st.dt)))  # `dt.astype(y0.dtype)` of the dense kernel
-                w = []
-                for r in range(st.ob, st.oe):
-                    x = float(Y((TT(ts[r]) - t0) / (t1 - t0)))
-                    p0, p1, pm, q0, q1 = quartic_weights(x, dts)
-                    w.append((p0 + pm, p1, pm, q0, q1))  # (y_mid = y0 + ...: its cotangent reaches y0 as well)
-                y0bar, ymbar, f0bar, f1bar = (torch.empty_like(lam) for _ in range(4))
-                be.dense_cotangent([y0bar, lam, ymbar, f0bar, f1bar], g[st.ob : st.oe], w, acc_mask=0b10)
+                y0bar, ymbar, f0bar, f1bar, dts = cot
             nus = [None] * (S + 1)
             for i in range(S, -1, -1):
                 terms = []
@@ -249,11 +287,7 @@ class StepsRun:
             if grads[0] is not None:
                 terms.append((as_operand(grads[0], like=lam), 1.0))
             self._accum_params(pg, grads[1:])
-        d = 1.0 if len(ts) < 2 or ts[-1] >= ts[0] else -1.0
-        e = 1
-        while e < len(ts) and d * ts[e] <= d * ts[0]:
-            e += 1
-        terms += [(g[r].view(shape), 1.0) for r in range(min(e, T_rows))]
+        terms += self._start_terms(g)
         gy0 = torch.empty_like(lam)
         while len(terms) > _hip.XDE_BP_MAX_X:  # (only with more than 14 rows at the start time)
             part = torch.empty_like(lam)
