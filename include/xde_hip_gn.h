@@ -1,7 +1,8 @@
 /*
- * xde_hip_gn.h — entry points of libxde_hip.so for sdeint with GENERAL or SCALAR noise (sdeint(..., solver=Euler,
- * options={"noise_type": "general" | "scalar"})): the Ito Euler-Maruyama step whose diffusion is a matrix per row of the state, and its
- * cotangents (host side: paddlexde_amd/solver/base_fixed_solver.py, paddlexde_amd/solver/_autograd.py).
+ * xde_hip_gn.h — entry points of libxde_hip.so for sdeint with GENERAL or SCALAR noise (sdeint(..., solver=Euler | Heun,
+ * options={"noise_type": "general" | "scalar"})): the Ito Euler-Maruyama step whose diffusion is a matrix per row of the state and its
+ * cotangents, and the two launches of the Stratonovich Heun (trapezoidal) step on such a diffusion with theirs (host side:
+ * paddlexde_amd/solver/base_fixed_solver.py, paddlexde_amd/solver/_autograd.py).
  *
  * Same conventions as xde_hip_sde.h (status codes, device pointers borrowed from the caller, `stream` = hipStream_t as void*,
  * XDE_F32 / XDE_F64, dt the step's size and s = sqrt(|dt|) rounded to the state dtype by the caller, both converted to the state dtype T
@@ -55,6 +56,59 @@ int xde_sde_gn_step(void* y1, const void* y0, const void* f, const void* g, int6
  */
 int xde_sde_gn_backward(void* gf, void* gg, const void* gy1, int64_t rows, int64_t D, int64_t M, double dt, double s, uint64_t seed,
                         int64_t k, int dtype, void* stream);
+
+/*
+ * HEUN (the stochastic trapezoidal rule: Stratonovich, strong order 1/2 in general and 1 for commutative noise), two launches around
+ * the evaluations f1 = drift(t1, yp), g1 = diffusion(t1, yp).  Composed from per-formula launches the step would stream g0 twice (for
+ * the predictor and again for the corrector) and g1 once; here the predictor KEEPS its matrix-vector product: it writes a0 = g0 w next
+ * to yp, and the corrector reads a0 (N elements) and streams only g1 — two streams of M N elements per step, not three.  Both use the w
+ * of (seed, k) above, and every sum over m is the step's: sequential in m for every launch shape.
+ *
+ * PREDICT, one launch, (3 + M) N elements read and 2 N written.  Per output o = r * D + d, in T:
+ *
+ *   a     = g0[o * M] * w[r, 0]
+ *   a     = a + g0[o * M + m] * w[r, m]         for m = 1 .. M - 1, in this order
+ *   a0[o] = a
+ *   yp[o] = (y0[o] + f0[o] * dt) + a
+ *
+ * yp has the bits of xde_sde_gn_step's y1 on the same operands.  No operand may overlap an output.
+ */
+int xde_sde_gn_heun_predict(void* yp, void* a0, const void* y0, const void* f0, const void* g0, int64_t rows, int64_t D, int64_t M,
+                            double dt, double s, uint64_t seed, int64_t k, int dtype, void* stream);
+
+/*
+ * CORRECT, one launch, (4 + M) N elements read and N written:
+ *
+ *   b     = g1[o * M] * w[r, 0]
+ *   b     = b + g1[o * M + m] * w[r, m]         for m = 1 .. M - 1, in this order
+ *   y1[o] = (y0[o] + (f0[o] + f1[o]) * (0.5 * dt)) + (a0[o] + b) * 0.5
+ *
+ * y1 may be y0 (an in-place step); no other overlap of y1 with an operand.
+ */
+int xde_sde_gn_heun_correct(void* y1, const void* y0, const void* f0, const void* f1, const void* a0, const void* g1, int64_t rows,
+                            int64_t D, int64_t M, double dt, double s, uint64_t seed, int64_t k, int dtype, void* stream);
+
+/*
+ * THE COTANGENTS OF BOTH, one launch that regenerates w from (seed, k).  From gy, the cotangent of the launch's state output, and gc, a
+ * second cotangent that reaches the matrix (null: none), with the scalars cf and ca converted to T:
+ *
+ *   h             = gy[o] * ca
+ *   c             = h + gc[o]                   (gc null: c = h;  gy null: c = gc[o])
+ *   gf[o]         = gy[o] * cf
+ *   ga[o]         = h
+ *   gg[o * M + m] = c * w[r, m]
+ *
+ * A null gf, ga or gg skips that output; all null: nothing to do (after the checks).  With gy null gc must be given, and gf and ga
+ * must be null.  With gg null no generator runs (s, seed are not read; k is still checked).  No output may overlap another operand.
+ *
+ * The corrector's cotangents are this launch at (cf, ca) = (0.5 * dt, 0.5) with gy = gy1 and gc null: gf is the cotangent of f0 and
+ * of f1, ga that of a0, gg that of g1 (the cotangent of y0 is gy1 itself; halving is exact, as for xde_sde_rheun_correct).  The
+ * predictor's are this launch at (cf, ca) = (dt, 1) with gy = gyp, gc = ga0 (the cotangent of its second output) and ga null: gf is
+ * the cotangent of f0 and gg[o * M + m] = (gyp[o] + ga0[o]) * w[r, m] that of g0 — both cotangents that reach g0 in one launch, so
+ * no M N elements are accumulated outside it; the cotangent of y0 is gyp itself.
+ */
+int xde_sde_gn_heun_backward(void* gf, void* ga, void* gg, const void* gy, const void* gc, int64_t rows, int64_t D, int64_t M, double cf,
+                             double ca, double s, uint64_t seed, int64_t k, int dtype, void* stream);
 
 #ifdef __cplusplus
 }

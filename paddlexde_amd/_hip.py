@@ -273,10 +273,13 @@ HEADERS["xde_hip_teval.h"] = {
     "xde_teval_dense": (_i32, [_vp, _vp, _vp, _vpp, _dp, _i32, _vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _i32, _i32, _i64, _i64, _i64, _i32, _vp]),
     "xde_teval_cotangent": (_i32, [_vpp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _i32, _i32, C.c_uint32, _i64, _i64, _i64, _i32, _vp]),
 }
-# the Euler-Maruyama step with general or scalar noise, and its cotangents
+# the Euler-Maruyama step with general or scalar noise and its cotangents; the Heun step's two launches on such noise and theirs
 HEADERS["xde_hip_gn.h"] = {
     "xde_sde_gn_step": (_i32, [_vp] * 4 + [_i64, _i64, _i64, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
     "xde_sde_gn_backward": (_i32, [_vp] * 3 + [_i64, _i64, _i64, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
+    "xde_sde_gn_heun_predict": (_i32, [_vp] * 5 + [_i64, _i64, _i64, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
+    "xde_sde_gn_heun_correct": (_i32, [_vp] * 6 + [_i64, _i64, _i64, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
+    "xde_sde_gn_heun_backward": (_i32, [_vp] * 5 + [_i64, _i64, _i64, _dbl, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
 }
 # ddeint_steps: the delayed states of one stage from the Hermite tape of the solution, and the fan of their cotangent into its nodes
 HEADERS["xde_hip_dde.h"] = {
@@ -1077,7 +1080,7 @@ class HipBackend:
     # -- the Euler-Maruyama step with general or scalar noise (include/xde_hip_gn.h) ---------------------------------------------------
     # Private for the reason _sde_em_step is.  Only FixedSolver._em_step under a non-diagonal BaseSDE (and its autograd node) call these.
     def _gn_call(self, who, state, mats, like, *scalars):
-        """The operand check the two general-noise entry points share; nothing is launched here.  ``state`` must be contiguous device
+        """The operand check the general-noise entry points share; nothing is launched here.  ``state`` must be contiguous device
         tensors of ``like``'s shape ``[.., D]`` and dtype and ``mats`` contiguous device tensors of shape ``[.., D, M]`` and that dtype,
         one M for all; None stands for a null pointer and is not checked (``like`` and one of ``mats`` are never None).  Returns
         ``(rows, D, M, tail)``, ``tail`` being ``scalars`` followed by the dtype code and the stream."""
@@ -1114,6 +1117,42 @@ class HipBackend:
         if rows == 0:
             return
         self._check(self.lib.xde_sde_gn_backward(_ptr(gf), _ptr(gg), _ptr(gy1), rows, D, int(M), *tail), "xde_sde_gn_backward")
+
+    # -- the Heun step with general or scalar noise (include/xde_hip_gn.h) --------------------------------------------------------------
+    # Private for the reason _sde_em_step is.  Only FixedSolver._heun_step under a non-diagonal BaseSDE (and its autograd nodes) call these.
+    def _sde_gn_heun_predict(self, yp, a0, y0, f0, g0, dt, s, seed, k):
+        """Heun's predictor: ``a0[.., d] = sum_m g0[.., d, m]*(s*Z[.., m])`` (sequential in m) and ``yp = (y0 + f0*dt) + a0``, ``yp`` the
+        bits of ``_sde_gn_step``'s output; Z as there.  One launch that streams ``g0`` once and keeps its product."""
+        rows, D, M, tail = self._gn_call("_sde_gn_heun_predict", (yp, a0, y0, f0), (g0,), y0, float(dt), float(s), int(seed), int(k))
+        if rows == 0:
+            return
+        rc = self.lib.xde_sde_gn_heun_predict(_ptr(yp), _ptr(a0), _ptr(y0), _ptr(f0), _ptr(g0), rows, D, M, *tail)
+        self._check(rc, "xde_sde_gn_heun_predict")
+
+    def _sde_gn_heun_correct(self, y1, y0, f0, f1, a0, g1, dt, s, seed, k):
+        """Heun's corrector: ``b = sum_m g1[.., d, m]*(s*Z[.., m])`` and ``y1 = (y0 + (f0 + f1)*(0.5*dt)) + (a0 + b)*0.5`` on the
+        predictor's ``a0`` and the same Z; ``y1`` may be ``y0``.  One launch that streams ``g1`` only."""
+        rows, D, M, tail = self._gn_call("_sde_gn_heun_correct", (y1, y0, f0, f1, a0), (g1,), y0, float(dt), float(s), int(seed), int(k))
+        if rows == 0:
+            return
+        rc = self.lib.xde_sde_gn_heun_correct(_ptr(y1), _ptr(y0), _ptr(f0), _ptr(f1), _ptr(a0), _ptr(g1), rows, D, M, *tail)
+        self._check(rc, "xde_sde_gn_heun_correct")
+
+    def _sde_gn_heun_backward(self, gf, ga, gg, gy, gc, M, cf, ca, s, seed, k):
+        """The cotangents of either launch: ``gf = gy*cf``, ``ga = gy*ca`` (``[.., D]``) and ``gg[.., d, m] = c[.., d]*(s*Z[.., m])``
+        (``[.., D, M]``) with ``c = gy*ca + gc`` (``gc`` None: ``gy*ca``; ``gy`` None: ``gc``, and then ``gf`` and ``ga`` are None);
+        any output may be None: skipped.  One launch regenerating the forward's Z."""
+        like = gy if gy is not None else gc
+        if like is None:
+            raise XdeError("_sde_gn_heun_backward: gy and gc are both None")
+        rows, D, M_, tail = self._gn_call("_sde_gn_heun_backward", (gf, ga, gy, gc), (gg,), like, float(cf), float(ca), float(s), int(seed),
+                                          int(k))
+        if M_ is not None and M_ != int(M):
+            raise XdeError("_sde_gn_heun_backward: gg's last axis is {}, M is {}".format(M_, int(M)))
+        if rows == 0:
+            return
+        rc = self.lib.xde_sde_gn_heun_backward(_ptr(gf), _ptr(ga), _ptr(gg), _ptr(gy), _ptr(gc), rows, D, int(M), *tail)
+        self._check(rc, "xde_sde_gn_heun_backward")
 
     # -- the Hermite tape of ddeint_steps (include/xde_hip_dde.h) ---------------------------------------------------------------------
     # Private for the reason _interp_rows is.  Only xde/steps_dde.py's autograd node (solver/_autograd.py: DdeTapeGatherFn) calls these.

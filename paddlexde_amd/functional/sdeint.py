@@ -8,7 +8,9 @@ derivative-free stochastic Runge-Kutta scheme SRI1W1 with ``solver=SRK`` (strong
 ``drift`` and 4 ``diffusion`` evaluations per step, on two in-kernel draws) — these three read the equation in the ITO sense — or by
 the reversible Heun scheme with ``solver=ReversibleHeun``, which reads it in the STRATONOVICH sense (strong order 1 under the same
 contract, 1/2 in general: two launches, one ``drift`` and one ``diffusion`` evaluation per step; the scheme ``sdeint_adjoint``
-differentiates in memory that does not grow with the number of steps), the Brownian
+differentiates in memory that does not grow with the number of steps), or by the Heun (stochastic trapezoidal) scheme with
+``solver=Heun``, STRATONOVICH as well (strong order 1 for commutative noise, 1/2 in general: two launches, two ``drift`` and two
+``diffusion`` evaluations per step; the one Stratonovich scheme that takes general and scalar noise, below), the Brownian
 increment ``sqrt(|dt|) * Z`` generated inside the kernel (include/xde_hip_sde.h).  The reference's version never ran (its ``fuse`` is a
 TODO and it calls an ``xde.format`` that does not exist); this is the step it meant.  The result has odeint's fixed-solver layout
 ``[..., T*L, D]``.  Gradients with respect to y0 and the parameters of ``drift`` and ``diffusion`` flow through the steps (the autograd
@@ -55,12 +57,16 @@ def sdeint(
     m, the sum over m taken sequentially.  One xde_sde_gn_step launch per step streams ``g`` once and builds the increment on chip; the
     backward is one launch that regenerates Z and keeps nothing of the forward but ``(dt, seed, k)`` (include/xde_hip_gn.h).
     ``"scalar"`` is general noise with ``M == 1`` (``diffusion`` returns ``y.shape + (1,)``); ``"diagonal"``, the default, is the
-    element-wise noise described above, unchanged.  Any other value is a ``ValueError``.  Milstein, SRK, ReversibleHeun,
-    ``sdeint_adjoint`` and ``logqp`` take diagonal noise only and say so."""
+    element-wise noise described above, unchanged.  Any other value is a ``ValueError``.  ``solver=Heun`` steps general and scalar
+    noise in the Stratonovich sense: ``yp = (y0 + f0*dt) + g0 @ w``, ``f1, g1`` at ``(t1, yp)``,
+    ``y1 = (y0 + (f0 + f1)*(0.5*dt)) + (g0 @ w + g1 @ w)*0.5`` on the same ``w = sqrt(|dt|) * Z`` and the same sequential sums; its
+    predictor launch keeps ``g0 @ w`` for the corrector, so a step streams the diffusion twice, not three times, and each launch's
+    backward regenerates Z (xde_sde_gn_heun_predict / _correct / _backward).  Milstein, SRK, ReversibleHeun, ``sdeint_adjoint`` and
+    ``logqp`` take diagonal noise only and say so."""
     if isinstance(y0, (tuple, list)):
         raise NotImplementedError("sdeint takes a tensor y0, not a tuple: stack the members into one state tensor")
     if not (isinstance(solver, type) and issubclass(solver, FixedSolver)):
-        raise NotImplementedError("sdeint steps with a fixed-step solver (solver=Euler, Euler-Maruyama, or solver=Milstein or SRK, or ReversibleHeun): adaptive steps would need "
+        raise NotImplementedError("sdeint steps with a fixed-step solver (solver=Euler, Euler-Maruyama, or solver=Milstein or SRK, or ReversibleHeun or Heun): adaptive steps would need "
                                   "a Brownian path that can be queried on any interval, which this library does not build")
     if not torch.is_tensor(t):
         t = torch.as_tensor(t)

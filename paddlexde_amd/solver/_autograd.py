@@ -1,4 +1,4 @@
-"""Autograd nodes around the step kernels (xde_stage_combine, xde_interp_rows, xde_sde_em_step, xde_sde_milstein_step, xde_sde_srk_*, xde_sde_rheun_*, xde_sde_kl_*, xde_sde_gn_*, xde_dde_tape_gather) for discretise-then-optimise training.
+"""Autograd nodes around the step kernels (xde_stage_combine, xde_interp_rows, xde_sde_em_step, xde_sde_milstein_step, xde_sde_srk_*, xde_sde_rheun_*, xde_sde_kl_*, xde_sde_gn_*, xde_sde_gn_heun_*, xde_dde_tape_gather) for discretise-then-optimise training.
 
 The reference trains by back-propagating through its eager solver ops (example/ode_demo.py:51-53:
 ``pred_y = odeint(func, batch_y0, t_span, solver=RK4); loss.backward()``).  Here the forward is one combine launch
@@ -149,6 +149,62 @@ class SdeGnEulerFn(torch.autograd.Function):
         if gf is not None or gg is not None:
             ctx.backend._sde_gn_backward(gf, gg, gy, ctx.M, *ctx.meta)
         return (None,) * 5 + (gy if need_y else None, gf, gg)
+
+
+class SdeGnHeunPredictFn(torch.autograd.Function):
+    """Heun's predictor with general or scalar noise (``HipBackend._sde_gn_heun_predict``) as an autograd node with two outputs: ``yp``,
+    SdeGnEulerFn's step, and ``a0 = g0 w``, the product the corrector takes instead of a second pass over ``g0``.  The node keeps only
+    ``(dt, s, seed, k)`` and M: backward is one xde_sde_gn_heun_backward launch at ``(cf, ca) = (dt, 1)`` that regenerates Z and takes
+    BOTH cotangents that reach ``g0`` — ``gg0 = (gyp + ga0) (x) w`` — so autograd accumulates no ``[.., D, M]`` tensor; ``gf0 = gyp*dt``
+    and ``gy0 = gyp`` (no launch).  An absent cotangent stays absent, an unwanted one None."""
+
+    @staticmethod
+    def forward(ctx, backend, dt, s, seed, k, y0, f0, g0):
+        yp, a0 = torch.empty_like(y0), torch.empty_like(y0)
+        backend._sde_gn_heun_predict(yp, a0, y0.detach(), f0.detach(), g0.detach(), dt, s, seed, k)
+        ctx.backend, ctx.meta, ctx.M = backend, (float(dt), float(s), int(seed), int(k)), int(g0.shape[-1])
+        ctx.set_materialize_grads(False)
+        return yp, a0
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gyp, ga0):
+        need_y, need_f, need_g = ctx.needs_input_grad[5:8]
+        gyp, ga0 = (None if x is None else _cotangent(x) for x in (gyp, ga0))
+        like = gyp if gyp is not None else ga0
+        dt, s, seed, k = ctx.meta
+        gf = torch.empty_like(gyp) if need_f and gyp is not None else None
+        gg = torch.empty(tuple(like.shape) + (ctx.M,), dtype=like.dtype, device=like.device) if need_g and like is not None else None
+        if gf is not None or gg is not None:
+            ctx.backend._sde_gn_heun_backward(gf, None, gg, gyp, ga0, ctx.M, dt, 1.0, s, seed, k)
+        return (None,) * 5 + (gyp if need_y else None, gf, gg)
+
+
+class SdeGnHeunCorrectFn(torch.autograd.Function):
+    """Heun's corrector with general or scalar noise, ``y1 = (y0 + (f0 + f1)*(0.5*dt)) + (a0 + g1 w)*0.5``
+    (``HipBackend._sde_gn_heun_correct``), as an autograd node.  The node keeps only ``(dt, s, seed, k)`` and M: backward is one
+    xde_sde_gn_heun_backward launch at ``(cf, ca) = (0.5*dt, 0.5)`` (halving is exact) whose ``gf`` is the cotangent of both ``f0`` and
+    ``f1``, ``ga`` that of ``a0`` and ``gg`` that of ``g1``, each only if wanted; ``gy0 = gy1`` needs no launch."""
+
+    @staticmethod
+    def forward(ctx, backend, dt, s, seed, k, y0, f0, f1, a0, g1):
+        out = torch.empty_like(y0)
+        backend._sde_gn_heun_correct(out, y0.detach(), f0.detach(), f1.detach(), a0.detach(), g1.detach(), dt, s, seed, k)
+        ctx.backend, ctx.meta, ctx.M = backend, (float(dt), float(s), int(seed), int(k)), int(g1.shape[-1])
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        need_y, need_f0, need_f1, need_a, need_g = ctx.needs_input_grad[5:10]
+        gy = _cotangent(gy)
+        dt, s, seed, k = ctx.meta
+        gf = torch.empty_like(gy) if need_f0 or need_f1 else None
+        ga = torch.empty_like(gy) if need_a else None
+        gg = torch.empty(tuple(gy.shape) + (ctx.M,), dtype=gy.dtype, device=gy.device) if need_g else None
+        if gf is not None or ga is not None or gg is not None:
+            ctx.backend._sde_gn_heun_backward(gf, ga, gg, gy, None, ctx.M, 0.5 * dt, 0.5, s, seed, k)
+        return (None,) * 5 + (gy if need_y else None, gf if need_f0 else None, gf if need_f1 else None, ga, gg)
 
 
 class SdeSupportFn(torch.autograd.Function):

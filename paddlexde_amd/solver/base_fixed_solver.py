@@ -22,7 +22,7 @@ from ..xde.base_ode import BaseODE
 from ..xde.base_sde import BaseSDE
 from ..xde.base_xde import BaseXDE
 from ._autograd import (CombineFn, InterpRowsFn, SdeEulerFn, SdeGnEulerFn, SdeKlAccFn, SdeKlEulerFn, SdeMilsteinFn, SdeRheunCorrectFn, SdeRheunPredictFn,
-                        SdeSrkStage1Fn, SdeSrkStage2Fn, SdeSrkStepFn, SdeSupportFn)
+                        SdeGnHeunCorrectFn, SdeGnHeunPredictFn, SdeSrkStage1Fn, SdeSrkStage2Fn, SdeSrkStepFn, SdeSupportFn)
 from ._common import as_operand, np_dtype, storage_ptr, t_span_to_host, upload
 
 _one_third = 1 / 3
@@ -124,7 +124,7 @@ class FixedSolver(metaclass=abc.ABCMeta):
     steps_sde = False  # the step is a convergent scheme for SDEs (a BaseSDE problem): Euler, as Euler-Maruyama, Milstein and SRK (Ito), ReversibleHeun (Stratonovich)
     steps_logqp = False  # the SDE step also accumulates the KL term of a latent SDE (sdeint's options logqp / prior_drift): Euler, Milstein
     logqp_refusal = "its step has no KL accumulation"  # why not, where steps_sde and not steps_logqp (SRK, ReversibleHeun)
-    steps_matrix_noise = False  # the SDE step takes general and scalar noise (BaseSDE(..., noise_type=...)): Euler (xde_sde_gn_step)
+    steps_matrix_noise = False  # the SDE step takes general and scalar noise (BaseSDE(..., noise_type=...)): Euler (xde_sde_gn_step), Heun (xde_sde_gn_heun_*)
     # why not, where steps_sde and not steps_matrix_noise (Milstein and SRK; ReversibleHeun states its own)
     matrix_noise_refusal = "its scheme assumes commutative, diagonal noise; for a [D, M] diffusion it would need Levy areas"
 
@@ -417,6 +417,38 @@ class FixedSolver(metaclass=abc.ABCMeta):
             return SdeRheunCorrectFn.apply(self.backend, dt, s, seed, k, y0, f0, f1, g0, g1), f0
         out = self._y1_out if self._y1_out is not None else torch.empty_like(y0)
         self.backend._sde_rheun_correct(out, y0, f0, f1, g0, g1, dt, s, 1, seed, k)
+        return out, f0
+
+    def _heun_step(self, t0, t1, dtt, y0, dt):
+        """One Heun (stochastic trapezoidal) step of a BaseSDE, Stratonovich, two launches around the evaluations they feed: predict
+        writes ``yp = (y0 + f0*dt) + g0*w``; then ``f1 = drift(t1, yp)``, ``g1 = diffusion(t1, yp)``; correct writes
+        ``y1 = (y0 + (f0 + f1)*(0.5*dt)) + (g0*w + g1*w)*0.5``, ``w = s*Z`` on the Z of (xde.seed, grid step k) as in ``_em_step``.
+        Under general or scalar noise ``g*w`` is the sequential sum over m of ``_em_step`` and the launches are xde_sde_gn_heun_predict,
+        which also writes ``a0 = g0*w``, and xde_sde_gn_heun_correct, which reads ``a0`` and streams only ``g1`` (include/xde_hip_gn.h;
+        SdeGnHeunPredictFn / SdeGnHeunCorrectFn when an operand is differentiated).  Under diagonal noise they are the launches that
+        exist: xde_sde_em_step and xde_sde_rheun_correct at direction +1, ``(g0 + g1)*(0.5*w)`` (SdeEulerFn / SdeRheunCorrectFn).
+        ``nfe`` counts evaluation points: two per step.  Returns ``(y1, f0)``."""
+        f0, g0, dt, s, _, _, k, grad = self._sde_prologue(t0, dtt, y0, dt)
+        self.nfe += 1
+        be, xde, seed, gn = self.backend, self.xde, self.xde.seed, self._matrix_noise
+        if grad:
+            yp, a0 = SdeGnHeunPredictFn.apply(be, dt, s, seed, k, y0, f0, g0) if gn else (SdeEulerFn.apply(be, dt, s, seed, k, y0, f0, g0), None)
+        else:
+            yp, a0 = torch.empty_like(y0), (torch.empty_like(y0) if gn else None)
+            if gn:
+                be._sde_gn_heun_predict(yp, a0, y0, f0, g0, dt, s, seed, k)
+            else:
+                be._sde_em_step(yp, y0, f0, g0, dt, s, seed, k)
+        f1, g1 = as_operand(xde.call_func(t1, yp), like=y0), (as_operand(xde.diffusion(t1, yp)) if gn else as_operand(xde.diffusion(t1, yp), like=y0))
+        if grad or (torch.is_grad_enabled() and (f1.requires_grad or g1.requires_grad)):
+            if gn:
+                return SdeGnHeunCorrectFn.apply(be, dt, s, seed, k, y0, f0, f1, a0, g1), f0
+            return SdeRheunCorrectFn.apply(be, dt, s, seed, k, y0, f0, f1, g0, g1), f0
+        out = self._y1_out if self._y1_out is not None else torch.empty_like(y0)
+        if gn:
+            be._sde_gn_heun_correct(out, y0, f0, f1, a0, g1, dt, s, seed, k)
+        else:
+            be._sde_rheun_correct(out, y0, f0, f1, g0, g1, dt, s, 1, seed, k)
         return out, f0
 
     def _combine_pre(self, y0, pre, ks, coef, dt, scale, out=None):
