@@ -18,6 +18,12 @@ weight clipping, one discriminator step and one generator step per iteration.
 
 ``--solver heun`` reads the generator's equation in the Stratonovich sense, as the paper does, with the trapezoidal ``solver=Heun``:
 two launches per step that stream ``g`` twice.  The default is Ito Euler-Maruyama.
+
+    python examples/sde_gan_demo.py --iters 200 --solver grheun --adjoint
+
+``--solver grheun`` is the paper's own scheme, reversible Heun on the ``[D, M]`` diffusion (``solver=GeneralReversibleHeun``:
+Stratonovich, one evaluation per step), and ``--adjoint`` trains the generator through ``sdeint_adjoint``, whose backward recomputes
+the path instead of keeping it: memory that does not grow with the number of steps.
 """
 import argparse
 import json
@@ -30,9 +36,9 @@ import torch.nn as nn
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from paddlexde_amd.functional import cdeint, sdeint  # noqa: E402
+from paddlexde_amd.functional import cdeint, sdeint, sdeint_adjoint  # noqa: E402
 from paddlexde_amd.interpolation import CubicHermiteSpline  # noqa: E402
-from paddlexde_amd.solver import RK4, Euler, Heun  # noqa: E402
+from paddlexde_amd.solver import RK4, Euler, GeneralReversibleHeun, Heun  # noqa: E402
 
 
 def make_data(device, batch=64, T=17, t1=2.0, theta=1.0, mu=0.0, sigma=0.5, seed=0):
@@ -51,9 +57,9 @@ def make_data(device, batch=64, T=17, t1=2.0, theta=1.0, mu=0.0, sigma=0.5, seed
 class Generator(nn.Module):
     """latent [B, V] -> series [B, T]: hidden state D, Brownian motion M, diffusion ``[B, 1, D, M]``."""
 
-    def __init__(self, latent=4, hidden=16, noise=3, width=32, solver=Euler):
+    def __init__(self, latent=4, hidden=16, noise=3, width=32, solver=Euler, adjoint=False):
         super().__init__()
-        self.latent, self.hidden, self.noise, self.solver = latent, hidden, noise, solver
+        self.latent, self.hidden, self.noise, self.solver, self.adjoint = latent, hidden, noise, solver, adjoint
         self.init = nn.Linear(latent, hidden)
         self.f_net = nn.Sequential(nn.Linear(hidden, width), nn.Softplus(), nn.Linear(width, hidden), nn.Tanh())
         self.g_net = nn.Sequential(nn.Linear(hidden, width), nn.Softplus(), nn.Linear(width, hidden * noise), nn.Tanh())
@@ -72,7 +78,11 @@ class Generator(nn.Module):
             options["step_size"] = step_size
         if seed is not None:
             options["seed"] = seed
-        xs = sdeint(self.f, self.g, x0, t, solver=self.solver, options=options)  # [B, T, D]
+        if self.adjoint and torch.is_grad_enabled():
+            params = tuple(self.f_net.parameters()) + tuple(self.g_net.parameters())
+            xs = sdeint_adjoint(self.f, self.g, x0, t, solver=self.solver, options=options, adjoint_params=params)
+        else:
+            xs = sdeint(self.f, self.g, x0, t, solver=self.solver, options=options)  # [B, T, D]
         return self.readout(xs).squeeze(-1)  # [B, T]
 
 
@@ -104,13 +114,13 @@ class Discriminator(nn.Module):
                 p.clamp_(-bound, bound)
 
 
-def train(iters=200, log_every=20, seed=0, device="cuda:0", batch=64, step_size=0.0625, solver=Euler):
+def train(iters=200, log_every=20, seed=0, device="cuda:0", batch=64, step_size=0.0625, solver=Euler, adjoint=False):
     """Alternate one discriminator and one generator step for ``iters`` iterations; returns one ``{"iters", "d_loss", "g_loss",
     "diffusion_grad"}`` per iteration, ``diffusion_grad`` the largest magnitude of the gradient the generator step left on the first
     weight of the generator's diffusion network."""
     torch.manual_seed(seed)
     t, real = make_data(device, batch=batch, seed=seed)
-    gen, dis = Generator(solver=solver).to(device), Discriminator().to(device)
+    gen, dis = Generator(solver=solver, adjoint=adjoint).to(device), Discriminator().to(device)
     g_opt = torch.optim.Adam(gen.parameters(), lr=2e-3, betas=(0.5, 0.9))
     d_opt = torch.optim.Adam(dis.parameters(), lr=4e-3, betas=(0.5, 0.9))
     latents = torch.Generator().manual_seed(seed + 1)
@@ -143,7 +153,9 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--step-size", type=float, default=0.0625, help="the generator's grid step under the observation times (0: step on the times)")
-    ap.add_argument("--solver", choices=("euler", "heun"), default="euler", help="the generator's scheme: Ito Euler-Maruyama, or Stratonovich Heun")
+    ap.add_argument("--solver", choices=("euler", "heun", "grheun"), default="euler",
+                    help="the generator's scheme: Ito Euler-Maruyama, Stratonovich Heun, or Stratonovich reversible Heun")
+    ap.add_argument("--adjoint", action="store_true", help="with --solver grheun: train through sdeint_adjoint (constant memory)")
     a = ap.parse_args()
-    hist = train(a.iters, step_size=a.step_size, solver={"euler": Euler, "heun": Heun}[a.solver])
+    hist = train(a.iters, step_size=a.step_size, solver={"euler": Euler, "heun": Heun, "grheun": GeneralReversibleHeun}[a.solver], adjoint=a.adjoint)
     print(json.dumps(hist[-1]))

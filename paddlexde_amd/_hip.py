@@ -280,6 +280,10 @@ HEADERS["xde_hip_gn.h"] = {
     "xde_sde_gn_heun_predict": (_i32, [_vp] * 5 + [_i64, _i64, _i64, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
     "xde_sde_gn_heun_correct": (_i32, [_vp] * 6 + [_i64, _i64, _i64, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
     "xde_sde_gn_heun_backward": (_i32, [_vp] * 5 + [_i64, _i64, _i64, _dbl, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
+    "xde_sde_gn_rheun_predict": (_i32, [_vp] * 6 + [_i64, _i64, _i64, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
+    "xde_sde_gn_rheun_seam": (_i32, [_vp] * 9 + [_i64, _i64, _i64, _dbl, _dbl, _i64, _dbl, _dbl, _i64, C.c_uint64, _i32, _vp]),
+    "xde_sde_gn_rheun_adjoint_stage": (_i32, [_vp] * 5 + [_i64, _i64, _i64, _dbl, _dbl, _i64, _dbl, _i64, C.c_uint64, _i32, _vp]),
+    "xde_sde_gn_rheun_adjoint_step": (_i32, [_vp] * 7 + [_i64, _dbl, _i32, _vp]),
 }
 # ddeint_steps: the delayed states of one stage from the Hermite tape of the solution, and the fan of their cotangent into its nodes
 HEADERS["xde_hip_dde.h"] = {
@@ -1153,6 +1157,56 @@ class HipBackend:
             return
         rc = self.lib.xde_sde_gn_heun_backward(_ptr(gf), _ptr(ga), _ptr(gg), _ptr(gy), _ptr(gc), rows, D, int(M), *tail)
         self._check(rc, "xde_sde_gn_heun_backward")
+
+    # -- the reversible Heun step with general or scalar noise and its cotangent sweep (include/xde_hip_gn.h) ----------------------------
+    # Private for the reason _interp_rows is.  Only FixedSolver._rheun_step under a non-diagonal BaseSDE, its autograd node and
+    # sdeint_adjoint's matrix-noise sweep call these.  dt and s carry the direction (the reverse step negates both).
+    def _sde_gn_rheun_predict(self, yh1, a, y, yh0, f, g, dt, s, seed, k):
+        """Reversible Heun's predictor: ``a[.., d] = sum_m g[.., d, m]*(s*Z[.., m])`` (sequential in m) and
+        ``yh1 = (((y + y) - yh0) + f*dt) + a``; Z as in ``_sde_gn_step``.  One launch that streams ``g`` once and keeps its product."""
+        rows, D, M, tail = self._gn_call("_sde_gn_rheun_predict", (yh1, a, y, yh0, f), (g,), y, float(dt), float(s), int(seed), int(k))
+        if rows == 0:
+            return
+        rc = self.lib.xde_sde_gn_rheun_predict(_ptr(yh1), _ptr(a), _ptr(y), _ptr(yh0), _ptr(f), _ptr(g), rows, D, M, *tail)
+        self._check(rc, "xde_sde_gn_rheun_predict")
+
+    def _sde_gn_rheun_seam(self, y1, yh2, a1, y0, f0, f1, a0, yh1, g1, dt0, s0, k0, dt1, s1, k1, seed):
+        """Step ``k0``'s corrector and step ``k1``'s predictor in one pass over ``g1``: ``y1`` with the bits of ``_sde_gn_heun_correct`` at
+        ``(dt0, s0, k0)`` and ``(yh2, a1)`` with those of ``_sde_gn_rheun_predict`` at ``(dt1, s1, k1)`` on ``y1, yh1, f1, g1``.  ``y1``
+        may be ``y0``; ``yh2`` may not be ``yh1``.  One launch."""
+        rows, D, M, tail = self._gn_call("_sde_gn_rheun_seam", (y1, yh2, a1, y0, f0, f1, a0, yh1), (g1,), y0, float(dt0), float(s0), int(k0),
+                                         float(dt1), float(s1), int(k1), int(seed))
+        if rows == 0:
+            return
+        rc = self.lib.xde_sde_gn_rheun_seam(_ptr(y1), _ptr(yh2), _ptr(a1), _ptr(y0), _ptr(f0), _ptr(f1), _ptr(a0), _ptr(yh1), _ptr(g1), rows, D, M,
+                                            *tail)
+        self._check(rc, "xde_sde_gn_rheun_seam")
+
+    def _sde_gn_rheun_adjoint_stage(self, bf, bg, af1, c1, ay1, dt, s0, k0, s1, k1, seed):
+        """The cotangents the sweep's vjp takes: ``bf = af1 + ay1*(0.5*dt)`` and ``bg[.., d, m] = c1[.., d]*w_k1[.., m] +
+        (ay1[.., d]*0.5)*w_k0[.., m]``; ``af1`` and ``c1`` None together: zero (the first backward step); ``ay1`` None: ``bg = c1 (x) w_k1``
+        and ``bf`` None.  ``bf`` may be ``af1``.  One launch regenerating both increments."""
+        like = ay1 if ay1 is not None else c1
+        if like is None:
+            raise XdeError("_sde_gn_rheun_adjoint_stage: ay1 and c1 are both None")
+        rows, D, M, tail = self._gn_call("_sde_gn_rheun_adjoint_stage", (bf, af1, c1, ay1), (bg,), like, float(dt), float(s0), int(k0), float(s1),
+                                         int(k1), int(seed))
+        if rows == 0:
+            return
+        rc = self.lib.xde_sde_gn_rheun_adjoint_stage(_ptr(bf), _ptr(bg), _ptr(af1), _ptr(c1), _ptr(ay1), rows, D, M, *tail)
+        self._check(rc, "xde_sde_gn_rheun_adjoint_stage")
+
+    def _sde_gn_rheun_adjoint_step(self, ay0, ayh0, af0, c0, ay1, ayh1, v, dt):
+        """One backward step of the state cotangents: ``A = ayh1 + v``, ``ay0 = ay1 + (A + A)``, ``ayh0 = -A``,
+        ``af0 = ay1*(0.5*dt) + A*dt``, ``c0 = ay1*0.5 + A``; ``ayh1`` None: zero.  ``ay0`` may be ``ay1`` and ``ayh0`` may be ``ayh1``.
+        One launch, no generator."""
+        self._require_device(ay0, ayh0, af0, c0, ay1, ayh1, v)
+        _require_alike("_sde_gn_rheun_adjoint_step", "operands", ay1, (ay0, ayh0, af0, c0, ay1, ayh1, v))
+        if ay1.numel() == 0:
+            return
+        rc = self.lib.xde_sde_gn_rheun_adjoint_step(_ptr(ay0), _ptr(ayh0), _ptr(af0), _ptr(c0), _ptr(ay1), _ptr(ayh1), _ptr(v), ay1.numel(), float(dt),
+                                                    dtype_code(ay1.dtype), self._stream(ay1))
+        self._check(rc, "xde_sde_gn_rheun_adjoint_step")
 
     # -- the Hermite tape of ddeint_steps (include/xde_hip_dde.h) ---------------------------------------------------------------------
     # Private for the reason _interp_rows is.  Only xde/steps_dde.py's autograd node (solver/_autograd.py: DdeTapeGatherFn) calls these.

@@ -1,5 +1,5 @@
 // The kernels and launch helpers of libxde_hip.so's general-noise entry points, shared by xde_sde_gn.hip (the Euler-Maruyama step, as it
-// was built) and xde_sde_gn_heun.hip (the Heun step): the Ito Euler-Maruyama step with general (and scalar) noise, and its cotangents (C ABI: include/xde_hip_gn.h; host:
+// was built), xde_sde_gn_heun.hip (the Heun step) and xde_sde_gn_rheun.hip (the reversible Heun step and its sweep): the Ito Euler-Maruyama step with general (and scalar) noise, and its cotangents (C ABI: include/xde_hip_gn.h; host:
 // paddlexde_amd/solver/base_fixed_solver.py, sdeint's option noise_type).
 //
 // The traffic is g: M elements per output against three for y0, f and y1.  A workgroup owns a TILE of TO consecutive outputs
@@ -62,7 +62,8 @@ struct GnArgs {
 
 // what the step kernel computes from its sum a over m: the Euler-Maruyama y1 = base + a; Heun's predictor, the same y1 and a itself
 // (a0); Heun's corrector, y1 = (y0 + (f0 + f1) * (0.5 dt)) + (a0 + a) * 0.5 on the a0 the predictor kept
-enum GnMode { kGnStep = 0, kGnPredict = 1, kGnCorrect = 2 };
+// reversible Heun's predictor (xde_sde_gn_rheun.hip): Heun's predictor on the base ((y0 + y0) - yh0) + f * dt, yh0 in the place of f1
+enum GnMode { kGnStep = 0, kGnPredict = 1, kGnCorrect = 2, kGnRPredict = 3 };
 
 // a tile of the outputs: its first output, how many it holds, the first state row it meets and its first output's place in that row
 struct GnTileAt {
@@ -99,7 +100,7 @@ template <typename T> __device__ __forceinline__ GnSpan gn_span(const T* p, int 
 // w[i * mc + (m - m0)] = s * Z[(r_lo + i) * M + m] for the tile's rows i < nrows and the chunk's m0 <= m < m0 + mc.  `whole` (the chunk
 // is all of M): the rows' increments are one contiguous run of Z, walked block by block; else one run of mc elements per row.
 template <typename T>
-__device__ __forceinline__ void gn_stage_noise(T* wbuf, int64_t r_lo, int nrows, int M, int m0, int mc, bool whole, T s, const GnArgs& a) {
+__device__ __forceinline__ void gn_stage_noise(T* wbuf, int64_t r_lo, int nrows, int M, int m0, int mc, bool whole, T s, uint32_t k, const GnArgs& a) {
   constexpr int W = Block<T>::W;
   const int runs = whole ? 1 : nrows;
   const int len = whole ? nrows * mc : mc;
@@ -110,7 +111,7 @@ __device__ __forceinline__ void gn_stage_noise(T* wbuf, int64_t r_lo, int nrows,
     const int64_t j = start / W + b;
     if (j * W >= start + len) continue;
     T z[W];
-    normals(uint64_t(j), a.k, a.key0, a.key1, 0u, z);
+    normals(uint64_t(j), k, a.key0, a.key1, 0u, z);
 #pragma unroll
     for (int v = 0; v < W; ++v) {
       const int64_t e = j * W + v;
@@ -180,8 +181,8 @@ __global__ __launch_bounds__(kBlock) void xde_sde_gn_step_kernel(GnArgs a) {
   const T* f = static_cast<const T*>(a.in[1]);
   const T* g = static_cast<const T*>(a.in[2]);
   T* y1 = static_cast<T*>(a.out[0]);
-  T* a0_out = static_cast<T*>(a.out[1]);             // kGnPredict
-  const T* f1 = static_cast<const T*>(a.in[3]);      // kGnCorrect
+  T* a0_out = static_cast<T*>(a.out[1]);             // kGnPredict, kGnRPredict
+  const T* f1 = static_cast<const T*>(a.in[3]);      // kGnCorrect (kGnRPredict: yh0)
   const T* a0_in = static_cast<const T*>(a.in[4]);   // kGnCorrect
   const T half = T(0.5), hdt = half * dt;
   const bool whole = M <= kGnChunk;
@@ -204,7 +205,11 @@ __global__ __launch_bounds__(kBlock) void xde_sde_gn_step_kernel(GnArgs a) {
           prev[j] = a0_in[x.o_lo + ol];
         }
       } else {
-        if (ol < x.cnt) base[j] = y0[x.o_lo + ol] + f[x.o_lo + ol] * dt;
+        if constexpr (MODE == kGnRPredict) {
+          if (ol < x.cnt) base[j] = ((y0[x.o_lo + ol] + y0[x.o_lo + ol]) - f1[x.o_lo + ol]) + f[x.o_lo + ol] * dt;
+        } else {
+          if (ol < x.cnt) base[j] = y0[x.o_lo + ol] + f[x.o_lo + ol] * dt;
+        }
       }
     }
     for (int m0 = 0; m0 < M; m0 += kGnChunk) {
@@ -219,7 +224,7 @@ __global__ __launch_bounds__(kBlock) void xde_sde_gn_step_kernel(GnArgs a) {
           gbuf[ol * ldp + m] = g[(x.o_lo + ol) * int64_t(M) + m0 + m];
         }
       }
-      gn_stage_noise<T>(wbuf, x.r_lo, nrows, M, m0, mc, whole, s, a);
+      gn_stage_noise<T>(wbuf, x.r_lo, nrows, M, m0, mc, whole, s, a.k, a);
       __syncthreads();
       // the next tile's span is on its way while this one is summed
       if (whole && tile + gridDim.x < ntiles) gn_fetch<T, NV>(g, gn_tile(tile + gridDim.x, a), M, regs, edge);
@@ -244,7 +249,7 @@ __global__ __launch_bounds__(kBlock) void xde_sde_gn_step_kernel(GnArgs a) {
     for (int j = 0; j < OUT; ++j) {
       const int ol = t + j * kBlock;
       if (ol < x.cnt) {
-        if constexpr (MODE == kGnPredict) a0_out[x.o_lo + ol] = acc[j];
+        if constexpr (MODE == kGnPredict || MODE == kGnRPredict) a0_out[x.o_lo + ol] = acc[j];
         if constexpr (MODE == kGnCorrect) y1[x.o_lo + ol] = base[j] + (prev[j] + acc[j]) * half;
         else y1[x.o_lo + ol] = base[j] + acc[j];
       }
@@ -313,7 +318,7 @@ __global__ __launch_bounds__(kBlock) void xde_sde_gn_backward_kernel(GnArgs a) {
           }
         }
       }
-      gn_stage_noise<T>(wbuf, x.r_lo, nrows, M, m0, mc, whole, s, a);
+      gn_stage_noise<T>(wbuf, x.r_lo, nrows, M, m0, mc, whole, s, a.k, a);
       __syncthreads();
       if (whole) {
         const int len = x.cnt * M;
@@ -433,11 +438,11 @@ template <bool EXT> int gn_launch_backward(const GnArgs& a, int dtype, hipStream
 
 // The one statement of the operand rule of every entry point: every given operand aligned to its element type, and no output over
 // another given operand.  `outs` and `ins` hold N elements each (nbytes), `mat_out` and `mat_in` N * M (gbytes); `in_place`: the first
-// output may BE the first input (not merely touch it).  Eight operands at most; nothing is allocated.
+// output may BE the first input (not merely touch it).  Twelve operands at most; nothing is allocated.
 inline int gn_check_operands(const char* who, std::initializer_list<const void*> outs, const void* mat_out, std::initializer_list<const void*> ins,
                              const void* mat_in, bool in_place, size_t nbytes, size_t gbytes, size_t esz, const char* rule) {
-  const void* p[8];
-  size_t n[8];
+  const void* p[12];
+  size_t n[12];
   int cnt = 0;
   for (const void* q : outs) p[cnt] = q, n[cnt++] = nbytes;
   p[cnt] = mat_out, n[cnt++] = gbytes;

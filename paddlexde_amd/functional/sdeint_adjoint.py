@@ -10,6 +10,11 @@ cotangents ``(a_y, a_yh, a_f, a_g)`` are taken one step back by xde_sde_rheun_ad
 discretisation — what back-propagating through ``sdeint(..., solver=ReversibleHeun)`` gives, up to rounding — with one drift and one
 diffusion evaluation per backward step and every buffer reused in place.
 
+With ``solver=GeneralReversibleHeun`` and general or scalar noise the sweep is the matrix-noise one (``_sweep_gn``): the same recursion
+on xde_sde_gn_rheun_* (include/xde_hip_gn.h).  The cotangent of the ``[.., D, M]`` diffusion is rank two per output, so the sweep carries
+one state-sized vector ``c`` in its place and one launch writes the matrix the vjp takes; the reconstruction streams each diffusion
+matrix once, corrector k and predictor k - 1 in one launch.  Three ``[.., D, M]`` buffers live at a time, whatever the step count.
+
 Any other solver is refused: Euler, Milstein and SRK steps cannot be recomputed backwards.
 """
 import torch
@@ -18,6 +23,7 @@ from torch.autograd.function import once_differentiable
 from .. import _hip
 from ..solver._common import as_operand
 from ..solver.base_fixed_solver import sde_step_scalars
+from ..solver.fixed_solver.grheun import GeneralReversibleHeun
 from ..solver.fixed_solver.rheun import ReversibleHeun
 from ..utils.ode_utils import _rms_norm
 from ..xde.base_sde import BaseSDE, check_noise_type
@@ -28,13 +34,16 @@ _MESSAGE = (
 )
 
 
-def _solve(drift, diffusion, y0, t, rtol, atol, options):
-    """The forward of ``sdeint(..., solver=ReversibleHeun)`` and what the sweep needs of it."""
+def _solve(drift, diffusion, y0, t, rtol, atol, options, solver_cls=ReversibleHeun):
+    """The forward of ``sdeint(..., solver=solver_cls)`` and what the sweep needs of it."""
     options = dict(options)
     seed = options.pop("seed", None)
-    options.pop("noise_type", None)  # ("diagonal": sdeint_adjoint has refused any other value)
-    xde = BaseSDE(f=drift, g=diffusion, y0=y0, t_span=t, seed=seed)
-    solver = ReversibleHeun(xde=xde, y0=xde.y0, rtol=rtol, atol=atol, **options)
+    noise_type = options.pop("noise_type", "diagonal")  # (other than "diagonal": sdeint_adjoint has refused it but for GeneralReversibleHeun)
+    if solver_cls is ReversibleHeun:
+        xde = BaseSDE(f=drift, g=diffusion, y0=y0, t_span=t, seed=seed)
+    else:
+        xde = BaseSDE(f=drift, g=diffusion, y0=y0, t_span=t, seed=seed, noise_type=noise_type)
+    solver = solver_cls(xde=xde, y0=xde.y0, rtol=rtol, atol=atol, **options)
     grid, grid_dev, plan, pred_len = solver._plan(t)
     solution = solver._walk(grid, grid_dev, plan, pred_len)
     yh_end = solver._carry[0] if len(grid) > 1 else None
@@ -44,9 +53,9 @@ def _solve(drift, diffusion, y0, t, rtol, atol, options):
 
 class _SdeintAdjointFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, drift, diffusion, t, rtol, atol, options, n_params, y0, *params):
+    def forward(ctx, drift, diffusion, t, rtol, atol, options, solver_cls, n_params, y0, *params):
         with torch.no_grad():
-            xde, solution, yh_end, grid, grid_dev, plan = _solve(drift, diffusion, y0.detach(), t, rtol, atol, options)
+            xde, solution, yh_end, grid, grid_dev, plan = _solve(drift, diffusion, y0.detach(), t, rtol, atol, options, solver_cls)
         ctx.xde, ctx.grid, ctx.grid_dev, ctx.plan = xde, grid, grid_dev, plan
         ctx.params = params
         ctx.shape = tuple(y0.shape)
@@ -57,9 +66,10 @@ class _SdeintAdjointFn(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, grad_out):
         solution, *rest = ctx.saved_tensors
-        grad_y0, grad_params, _ = _sweep(ctx.xde, ctx.params, solution, rest[0] if rest else None, ctx.grid, ctx.grid_dev, ctx.plan,
-                                         grad_out, ctx.shape)
-        return (None,) * 7 + (grad_y0 if ctx.needs_input_grad[7] else None,) + tuple(grad_params)
+        sweep = _sweep if ctx.xde.noise_type == "diagonal" else _sweep_gn
+        grad_y0, grad_params, _ = sweep(ctx.xde, ctx.params, solution, rest[0] if rest else None, ctx.grid, ctx.grid_dev, ctx.plan,
+                                        grad_out, ctx.shape)
+        return (None,) * 8 + (grad_y0 if ctx.needs_input_grad[8] else None,) + tuple(grad_params)
 
 
 def _row(x, j, L, shape):
@@ -148,6 +158,97 @@ def _sweep(xde, params, solution, yh_end, grid, grid_dev, plan, grad_out, shape)
     return grad_y0, acc, y
 
 
+def _sweep_gn(xde, params, solution, yh_end, grid, grid_dev, plan, grad_out, shape):
+    """``_sweep`` under general or scalar noise.  Per backward step k: xde_sde_gn_rheun_adjoint_stage writes ``(bf, bg)`` from
+    ``(a_f, c, a_y)`` and the regenerated increments of steps k and k + 1; one vjp of ``(drift, diffusion)`` at ``yh``;
+    xde_sde_gn_rheun_adjoint_step takes ``(a_y, a_yh, a_f, c)`` one step back; then the state one grid point back.  The reconstruction
+    is one xde_sde_gn_rheun_predict launch at direction -1 to start, then per step one xde_sde_gn_rheun_seam launch at direction -1 —
+    corrector k and predictor k - 1 over the one ``gh`` — and a bare corrector at step 0.  ``bg`` is one reused buffer."""
+    backend = _hip.get_backend()
+    seed = xde.seed
+    L = shape[-2]
+    n_steps = len(grid) - 1
+    params = tuple(params)
+    wanted = [i for i, p in enumerate(params) if p.requires_grad]
+    acc = [None] * len(params)
+    a_y = as_operand(_row(grad_out, 0, L, shape)).clone()
+    if n_steps == 0:
+        for j in range(1, grad_out.shape[-2] // L):
+            a_y.add_(_row(grad_out, j, L, shape))
+        return a_y, acc, _row(solution, 0, L, shape)
+    a_0 = a_y
+    a_y = torch.zeros_like(a_0)
+
+    def evaluate(k, yh):
+        with torch.enable_grad():
+            yh = yh.detach().requires_grad_(True)
+            t = grid_dev[k : k + 1]
+            return yh, as_operand(xde.call_func(t, yh), like=yh), as_operand(xde.diffusion(t, yh))
+
+    def vjp(yh, f, g, bf, bg):
+        outs = [x for x in (f, g) if x.requires_grad]
+        cots = [b for x, b in ((f, bf), (g, bg)) if x.requires_grad]
+        if not outs:
+            return torch.zeros_like(bf)
+        got = torch.autograd.grad(outs, (yh,) + tuple(params[i] for i in wanted), cots, allow_unused=True)
+        for i, gp in zip(wanted, got[1:]):
+            if gp is not None:
+                acc[i] = gp.clone() if acc[i] is None else acc[i].add_(gp)
+        return as_operand(got[0]) if got[0] is not None else torch.zeros_like(bf)
+
+    def inject(k, end):
+        rows = plan.rows[k]
+        if plan.plain:
+            if end:
+                for j, _, _ in rows:
+                    a_y.add_(_row(grad_out, j, L, shape))
+            return
+        w5 = []
+        for _, kind, w in rows:
+            wb = 1.0 if kind == _hip.XDE_ROW_COPY_B else (0.0 if kind == _hip.XDE_ROW_COPY_A else float(w[0]))
+            w5.append((1.0 - wb, wb, 0.0, 0.0, 0.0))
+        if not any(x[end] != 0.0 for x in w5):
+            return
+        g_rows = torch.stack([_row(grad_out, j, L, shape) for j, _, _ in rows])
+        outs = [None] * 5
+        outs[end] = a_y
+        backend.dense_cotangent(outs, g_rows, w5, acc_mask=1 << end)
+
+    def scalars(k):
+        return sde_step_scalars(grid[k + 1] - grid[k], solution.dtype)
+
+    y = as_operand(_row(solution, grad_out.shape[-2] // L - 1, L, shape)).clone()
+    yh, f, g = evaluate(n_steps, yh_end)
+    a_f, c, bg = torch.empty_like(y), torch.empty_like(y), torch.empty_like(g)
+    a_yh, yh0, a = torch.empty_like(y), torch.empty_like(y), torch.empty_like(y)
+    dt, s = scalars(n_steps - 1)
+    # (the reverse predictor of the last step: yh at grid point n - 1, and a = gh_n (-w_{n-1}) for that step's reverse corrector)
+    backend._sde_gn_rheun_predict(yh0, a, y, yh.detach(), f.detach(), g.detach(), -dt, -s, seed, n_steps - 1)
+    for k in range(n_steps - 1, -1, -1):
+        dt, s = scalars(k)
+        first = k == n_steps - 1
+        inject(k, 1)
+        s1 = 0.0 if first else scalars(k + 1)[1]
+        backend._sde_gn_rheun_adjoint_stage(a_f, bg, None if first else a_f, None if first else c, a_y, dt, s, k, s1, k + 1, seed)
+        v = vjp(yh, f, g, a_f, bg)
+        backend._sde_gn_rheun_adjoint_step(a_y, a_yh, a_f, c, a_y, None if first else a_yh, v, dt)
+        del v
+        # the state one grid point back: corrector k at direction -1 and, in the same pass over gh_k, predictor k - 1
+        f1 = f.detach()
+        yh, f, g = evaluate(k, yh0)
+        if k == 0:
+            backend._sde_gn_heun_correct(y, y, f1, f.detach(), a, g.detach(), -dt, -s, seed, k)
+        else:
+            dtp, sp = scalars(k - 1)
+            yh0, a1 = torch.empty_like(y), torch.empty_like(y)  # (yh holds the buffer before: the evaluation's graph reads it)
+            backend._sde_gn_rheun_seam(y, yh0, a1, y, f1, f.detach(), a, yh.detach(), g.detach(), -dt, -s, k, -dtp, -sp, k - 1, seed)
+            a = a1
+        inject(k, 0)
+    backend._sde_gn_rheun_adjoint_stage(None, bg, None, c, None, 0.0, 0.0, 0, scalars(0)[1], 0, seed)  # (bg = c (x) w_0)
+    grad_y0 = a_y.add_(a_yh).add_(vjp(yh, f, g, a_f, bg)).add_(a_0)
+    return grad_y0, acc, y
+
+
 def sdeint_adjoint(
     drift: callable,
     diffusion: callable,
@@ -179,11 +280,11 @@ def sdeint_adjoint(
                                       "sdeint(..., solver=Euler) or solver=Milstein, which keep the steps' operands for the "
                                       "backward".format(key))
     noise_type = check_noise_type(dict(options).get("noise_type", "diagonal"))
-    if noise_type != "diagonal":
+    if noise_type != "diagonal" and solver is not GeneralReversibleHeun:
         raise NotImplementedError("sdeint_adjoint does not take options['noise_type'] = {!r}: the reversible Heun kernels and their "
                                   "cotangent sweep are diagonal (general noise for them is a follow-up); sdeint(..., solver=Euler) "
                                   "steps general and scalar noise and keeps the steps' operands for the backward".format(noise_type))
-    if solver is not ReversibleHeun:
+    if solver is not ReversibleHeun and solver is not GeneralReversibleHeun:
         raise NotImplementedError(_MESSAGE)
     for name, value in (("adjoint_solver", adjoint_solver), ("adjoint_rtol", adjoint_rtol), ("adjoint_atol", adjoint_atol),
                         ("adjoint_options", adjoint_options), ("event_fn", event_fn)):
@@ -210,4 +311,4 @@ def sdeint_adjoint(
     if torch.is_grad_enabled() and t.requires_grad:
         raise NotImplementedError("sdeint_adjoint gives no gradient with respect to t; detach t (gradients reach y0 and the "
                                   "adjoint_params)")
-    return _SdeintAdjointFn.apply(drift, diffusion, t, rtol, atol, options, len(params), y0, *params)
+    return _SdeintAdjointFn.apply(drift, diffusion, t, rtol, atol, options, solver, len(params), y0, *params)

@@ -207,6 +207,34 @@ class SdeGnHeunCorrectFn(torch.autograd.Function):
         return (None,) * 5 + (gy if need_y else None, gf if need_f0 else None, gf if need_f1 else None, ga, gg)
 
 
+class SdeGnRheunPredictFn(torch.autograd.Function):
+    """Reversible Heun's predictor with general or scalar noise (``HipBackend._sde_gn_rheun_predict``) as an autograd node with two
+    outputs: ``yh1 = (((y0 + y0) - yh0) + f0*dt) + a`` and ``a = g0 w``, the product the corrector takes.  The node keeps only
+    ``(dt, s, seed, k)`` and M: backward is SdeGnHeunPredictFn's launch — xde_sde_gn_heun_backward at ``(cf, ca) = (dt, 1)`` with
+    ``gy = gyh1`` and ``gc = ga`` — and ``gy0 = gyh1 + gyh1``, ``gyh0 = -gyh1``.  An absent cotangent stays absent, an unwanted one None."""
+
+    @staticmethod
+    def forward(ctx, backend, dt, s, seed, k, y0, yh0, f0, g0):
+        yh1, a = torch.empty_like(y0), torch.empty_like(y0)
+        backend._sde_gn_rheun_predict(yh1, a, y0.detach(), yh0.detach(), f0.detach(), g0.detach(), dt, s, seed, k)
+        ctx.backend, ctx.meta, ctx.M = backend, (float(dt), float(s), int(seed), int(k)), int(g0.shape[-1])
+        ctx.set_materialize_grads(False)
+        return yh1, a
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gyh, ga):
+        need_y, need_yh, need_f, need_g = ctx.needs_input_grad[5:9]
+        gyh, ga = (None if x is None else _cotangent(x) for x in (gyh, ga))
+        like = gyh if gyh is not None else ga
+        dt, s, seed, k = ctx.meta
+        gf = torch.empty_like(gyh) if need_f and gyh is not None else None
+        gg = torch.empty(tuple(like.shape) + (ctx.M,), dtype=like.dtype, device=like.device) if need_g and like is not None else None
+        if gf is not None or gg is not None:
+            ctx.backend._sde_gn_heun_backward(gf, None, gg, gyh, ga, ctx.M, dt, 1.0, s, seed, k)
+        return (None,) * 5 + (gyh + gyh if need_y and gyh is not None else None, -gyh if need_yh and gyh is not None else None, gf, gg)
+
+
 class SdeSupportFn(torch.autograd.Function):
     """Milstein's support point ``yb = (y0 + f*dt) + g*s`` (``HipBackend._sde_milstein_support``) as an autograd node: backward is one
     launch writing ``gf = gyb*dt`` and ``gg = gyb*s`` (xde_sde_milstein_support_backward); ``gy0 = gyb`` needs no launch."""

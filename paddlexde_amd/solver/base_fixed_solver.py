@@ -22,7 +22,7 @@ from ..xde.base_ode import BaseODE
 from ..xde.base_sde import BaseSDE
 from ..xde.base_xde import BaseXDE
 from ._autograd import (CombineFn, InterpRowsFn, SdeEulerFn, SdeGnEulerFn, SdeKlAccFn, SdeKlEulerFn, SdeMilsteinFn, SdeRheunCorrectFn, SdeRheunPredictFn,
-                        SdeGnHeunCorrectFn, SdeGnHeunPredictFn, SdeSrkStage1Fn, SdeSrkStage2Fn, SdeSrkStepFn, SdeSupportFn)
+                        SdeGnHeunCorrectFn, SdeGnHeunPredictFn, SdeGnRheunPredictFn, SdeSrkStage1Fn, SdeSrkStage2Fn, SdeSrkStepFn, SdeSupportFn)
 from ._common import as_operand, np_dtype, storage_ptr, t_span_to_host, upload
 
 _one_third = 1 / 3
@@ -225,11 +225,12 @@ class FixedSolver(metaclass=abc.ABCMeta):
         self._acc = None  # logqp: the running KL sum of every row the last step left (float64 y0.shape[:-1]; None: zero)
 
     # -- per-step state ---------------------------------------------------------------------------
-    def _arm(self, dt=None, t0_host=None, row=None, y1_out=None, k=None, ctrls=None, rec=None):
+    def _arm(self, dt=None, t0_host=None, row=None, y1_out=None, k=None, ctrls=None, rec=None, dt_next=None):
         """The state ``step`` reads while a walk drives it, set here and nowhere else.  ``_arm()`` is the idle state, in which a
         ``step()`` called from outside reads its times from the device: whoever arms does so inside a ``try`` whose ``finally`` is
         ``self._arm()``, so the state is idle again also after ``func`` raised or a capture was refused."""
         self._dt = dt  # host dt (numpy scalar of the time dtype)
+        self._dt_next = dt_next  # host dt of the walk's next grid step (None: the last step, or outside a walk)
         self._t0_host = t0_host  # host t0 of the step
         self._row = row  # the step's row of the uploaded time table
         self._y1_out = y1_out  # where the step's final combine should write (a slice of the output, a hand-over buffer)
@@ -397,6 +398,8 @@ class FixedSolver(metaclass=abc.ABCMeta):
         The carried ``(yh, fh, gh)`` lives in ``self._carry``: at grid step 0 and on a step() outside a walk it is
         ``(y0, drift(t0, y0), diffusion(t0, y0))``, afterwards what the step before left.  Through SdeRheunPredictFn /
         SdeRheunCorrectFn when an operand is differentiated.  ``nfe`` counts steps.  Returns ``(y1, fh0)``."""
+        if self._matrix_noise:
+            return self._gn_rheun_step(t0, t1, dtt, y0, dt)
         self.nfe += 1
         xde, seed = self.xde, self.xde.seed
         k = self._k if self._k is not None else 0
@@ -417,6 +420,45 @@ class FixedSolver(metaclass=abc.ABCMeta):
             return SdeRheunCorrectFn.apply(self.backend, dt, s, seed, k, y0, f0, f1, g0, g1), f0
         out = self._y1_out if self._y1_out is not None else torch.empty_like(y0)
         self.backend._sde_rheun_correct(out, y0, f0, f1, g0, g1, dt, s, 1, seed, k)
+        return out, f0
+
+    def _gn_rheun_step(self, t0, t1, dtt, y0, dt):
+        """``_rheun_step`` under general or scalar noise (GeneralReversibleHeun): ``g*w`` is the sequential sum over m of ``_em_step``.
+        Predict (xde_sde_gn_rheun_predict) writes ``yh1 = (((y0 + y0) - yh0) + fh0*dt) + a`` and keeps ``a = gh0*w``; correct is
+        xde_sde_gn_heun_correct on ``(fh0, fh1, a, gh1)``: ``y1 = (y0 + (fh0 + fh1)*(0.5*dt)) + (a + gh1*w)*0.5``.  ``self._carry`` is
+        ``(yh, fh, gh, ahead)``.  Where nothing is differentiated and the walk knows its next step, ONE xde_sde_gn_rheun_seam launch takes
+        the corrector's place: it also does the next step's predictor in the same pass over ``gh1`` and leaves ``ahead = (yh2, a1)``, and
+        the next step launches no predictor.  Otherwise ``ahead`` is None and the two launches are separate (SdeGnRheunPredictFn /
+        SdeGnHeunCorrectFn when an operand is differentiated).  Both routes give the same bits.  ``nfe`` counts steps."""
+        self.nfe += 1
+        be, xde, seed = self.backend, self.xde, self.xde.seed
+        k = self._k if self._k is not None else 0
+        if not self._k or self._carry is None:
+            f, g = self.move(t0, dtt, y0)
+            self._carry = (y0, as_operand(f, like=y0), as_operand(g), None)
+        yh0, f0, g0, ahead = self._carry
+        dt, s = sde_step_scalars(dt, y0.dtype)
+        grad = torch.is_grad_enabled() and any(x.requires_grad for x in (y0, yh0, f0, g0))
+        if ahead is not None:
+            yh1, a0 = ahead  # (the step before's seam launch)
+        elif grad:
+            yh1, a0 = SdeGnRheunPredictFn.apply(be, dt, s, seed, k, y0, yh0, f0, g0)
+        else:
+            yh1, a0 = torch.empty_like(y0), torch.empty_like(y0)
+            be._sde_gn_rheun_predict(yh1, a0, y0, yh0, f0, g0, dt, s, seed, k)
+        f1, g1 = as_operand(xde.call_func(t1, yh1), like=y0), as_operand(xde.diffusion(t1, yh1))
+        if grad or (torch.is_grad_enabled() and (f1.requires_grad or g1.requires_grad or a0.requires_grad)):
+            self._carry = (yh1, f1, g1, None)
+            return SdeGnHeunCorrectFn.apply(be, dt, s, seed, k, y0, f0, f1, a0, g1), f0
+        out = self._y1_out if self._y1_out is not None else torch.empty_like(y0)
+        if self._dt_next is None:
+            self._carry = (yh1, f1, g1, None)
+            be._sde_gn_heun_correct(out, y0, f0, f1, a0, g1, dt, s, seed, k)
+            return out, f0
+        dt1, s1 = sde_step_scalars(self._dt_next, y0.dtype)
+        yh2, a1 = torch.empty_like(y0), torch.empty_like(y0)
+        be._sde_gn_rheun_seam(out, yh2, a1, y0, f0, f1, a0, yh1, g1, dt, s, k, dt1, s1, k + 1, seed)
+        self._carry = (yh1, f1, g1, (yh2, a1))
         return out, f0
 
     def _heun_step(self, t0, t1, dtt, y0, dt):
@@ -615,7 +657,8 @@ class FixedSolver(metaclass=abc.ABCMeta):
                     dst = out.narrow(-2, jb * L, L)
                     dst_b = dst.view(y0.shape) if (direct and dst.data_ptr() % 16 == 0) else None
                 y1_out = None if own_state else (dst_b if dst_b is not None else (bufs[k % 2] if bufs is not None else None))
-                self._arm(grid[k + 1] - grid[k], grid[k], table[k] if table is not None else None, y1_out, k)
+                self._arm(grid[k + 1] - grid[k], grid[k], table[k] if table is not None else None, y1_out, k,
+                          dt_next=grid[k + 2] - grid[k + 1] if k + 2 <= n_steps else None)
                 acc_a = self._acc
                 y1, f_a = self.step(t0, t1, y)
                 if cum is not None:
