@@ -21,6 +21,9 @@ with one RK4 step per window on the piecewise linear path through them; the fiel
 
     python examples/cde_demo.py --max-steps 60 [--adjoint] [--control natural [--irregular] [--missing 0.3]] [--encoder]
     python examples/cde_demo.py --max-steps 60 --logsig 2 --window 8
+
+``--fused-head`` builds the field as a ``CDELinearHead``: its first ``Linear + Tanh`` is the trunk, and the last ``Linear``, the ``tanh``
+and the contraction with ``X'(t)`` run as one launch — ``[B, H, C]`` is never written.
 """
 import argparse
 import math
@@ -37,6 +40,7 @@ from paddlexde_amd.functional import cdeint, cdeint_adjoint  # noqa: E402
 from paddlexde_amd.interpolation import (CubicHermiteSpline, LinearInterpolation, NaturalCubicSpline, logsig_path,  # noqa: E402
                                          logsignature_channels)
 from paddlexde_amd.solver import RK4, Dopri5  # noqa: E402
+from paddlexde_amd.xde import CDELinearHead  # noqa: E402
 
 CHANNELS = 3  # (time, x, y)
 
@@ -78,6 +82,17 @@ class CDEFunc(nn.Module):
         return self.net(z).reshape(z.shape + (self.channels,))
 
 
+class Trunk(nn.Module):
+    """The first ``Linear + Tanh`` of ``CDEFunc``, as ``CDELinearHead`` takes it: ``(t, z) -> [B, 32]``."""
+
+    def __init__(self, hidden):
+        super().__init__()
+        self.net = nn.Sequential(nn.Linear(hidden, 32), nn.Tanh())
+
+    def forward(self, t, z):
+        return self.net(z)
+
+
 class ChannelAffine(nn.Module):
     """series [B, T, C] -> the same with x and y scaled and shifted per channel (starts as the identity).  Time passes through; a NaN
     entry stays NaN and takes no part in the gradient."""
@@ -95,10 +110,10 @@ class ChannelAffine(nn.Module):
 
 
 class NeuralCDE(nn.Module):
-    def __init__(self, hidden=8, encoder=False, channels=CHANNELS):
+    def __init__(self, hidden=8, encoder=False, channels=CHANNELS, fused_head=False):
         super().__init__()
         self.initial = nn.Linear(CHANNELS, hidden)
-        self.func = CDEFunc(hidden, channels)
+        self.func = CDELinearHead(Trunk(hidden), 32, hidden, channels) if fused_head else CDEFunc(hidden, channels)
         self.readout = nn.Linear(hidden, 1)
         if encoder:
             self.encoder = ChannelAffine()
@@ -116,11 +131,11 @@ class NeuralCDE(nn.Module):
 
 
 def train(max_steps=60, n=128, length=32, hidden=8, seed=0, device="cuda:0", adjoint=False, log_every=10, control="cubic", irregular=False,
-          missing=0.0, encoder=False, logsig=0, window=8):
+          missing=0.0, encoder=False, logsig=0, window=8, fused_head=False):
     if logsig:
         if adjoint or encoder or irregular or missing > 0.0 or control != "cubic":
             raise ValueError("--logsig runs on its own: RK4 on the piecewise linear path through the windows' logsignatures")
-        return train_logsig(max_steps, n, 8 * length + 1, hidden, seed, device, log_every, logsig, window)
+        return train_logsig(max_steps, n, 8 * length + 1, hidden, seed, device, log_every, logsig, window, fused_head)
     if control not in ("cubic", "natural"):
         raise ValueError("control must be 'cubic' or 'natural', got {!r}".format(control))
     if control == "cubic" and (irregular or missing > 0.0):
@@ -131,7 +146,7 @@ def train(max_steps=60, n=128, length=32, hidden=8, seed=0, device="cuda:0", adj
     make = (lambda x, **kw: CubicHermiteSpline(x, **kw)) if control == "cubic" else (
         lambda x, **kw: NaturalCubicSpline(x, series[0, :, 0], **kw))  # (channel 0 is the time)
     X = None if encoder else make(series)
-    model = (NeuralCDE(hidden, encoder=True) if encoder else NeuralCDE(hidden)).to(device)
+    model = NeuralCDE(hidden, encoder=encoder, fused_head=fused_head).to(device)
     opt = torch.optim.Adam(model.parameters(), lr=1e-2)
     losses = []
     t0 = time.perf_counter()
@@ -154,13 +169,13 @@ def train(max_steps=60, n=128, length=32, hidden=8, seed=0, device="cuda:0", adj
     return losses
 
 
-def train_logsig(max_steps, n, length, hidden, seed, device, log_every, depth, window):
+def train_logsig(max_steps, n, length, hidden, seed, device, log_every, depth, window, fused_head=False):
     """The log-ODE method: the control is the piecewise linear path through the cumulated logsignatures of the windows (built once: the
     series is data), the field has one column per logsignature channel, and RK4 takes one step per window."""
     torch.manual_seed(seed)
     series, labels = make_data(n, length, seed, device)
     X = LinearInterpolation(logsig_path(series, depth, window))
-    model = NeuralCDE(hidden, channels=logsignature_channels(CHANNELS, depth)).to(device)
+    model = NeuralCDE(hidden, channels=logsignature_channels(CHANNELS, depth), fused_head=fused_head).to(device)
     opt = torch.optim.Adam(model.parameters(), lr=1e-2)
     losses = []
     t0 = time.perf_counter()
@@ -188,7 +203,8 @@ if __name__ == "__main__":
     ap.add_argument("--encoder", action="store_true", help="train a per-channel affine in front of the spline through differentiable=True")
     ap.add_argument("--logsig", type=int, default=0, metavar="DEPTH", help="the log-ODE method: windows of logsignatures of this depth (1 or 2)")
     ap.add_argument("--window", type=int, default=8, metavar="L", help="steps per logsignature window (with --logsig)")
+    ap.add_argument("--fused-head", action="store_true", help="the field as a CDELinearHead: last layer, tanh and contraction in one launch")
     a = ap.parse_args()
     ls = train(a.max_steps, adjoint=a.adjoint, control=a.control, irregular=a.irregular, missing=a.missing, encoder=a.encoder,
-               logsig=a.logsig, window=a.window)
+               logsig=a.logsig, window=a.window, fused_head=a.fused_head)
     print("first loss {:.4f} -> last loss {:.4f}".format(ls[0], ls[-1]))

@@ -262,6 +262,21 @@ HEADERS["xde_hip_cdegrad.h"] = {
     "xde_spline_natural_coeffs_backward_workspace_bytes": (_i64, [_i64, _i32, _i32, _i32]),
     "xde_spline_natural_gather_backward": (_i32, [_vp] * 6 + [_i64, _i32, _i32, _i32, _i32, _vp]),
 }
+
+
+class XdeCdeHeadPlan(C.Structure):
+    """Mirror of xde_cdehead_plan_t (include/xde_hip_cdehead.h)."""
+
+    _fields_ = [(name, C.c_int32) for name in ("served", "tile_b", "tile_n", "pass_n", "kh", "kq", "kq_regs", "S", "Hc", "lds_dx",
+                                               "lds_bytes", "k_cap")] + [("items", C.c_int64), ("blocks", C.c_int64)]
+
+
+# a CDE field's last linear layer, its activation and the contraction as one launch, and the cotangent of its pre-activations
+HEADERS["xde_hip_cdehead.h"] = {
+    "xde_cdehead_forward": (_i32, [_vp] * 8 + [_dbl, _i32, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "xde_cdehead_backward": (_i32, [_vp] * 9 + [_dbl, _i32, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "xde_cdehead_plan": (_i32, [_i64, _i32, _i32, _i32, _i32, _i32, C.POINTER(XdeCdeHeadPlan)]),
+}
 # the KL term of a latent SDE fused into the Euler-Maruyama step, and its cotangents
 HEADERS["xde_hip_kl.h"] = {
     "xde_sde_kl_step": (_i32, [_vp] * 7 + [_i64, _i64, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
@@ -324,6 +339,9 @@ XDE_INTERP_MAX_ROWS = 8
 XDE_INTERP_LINEAR, XDE_INTERP_CUBIC = 0, 1
 XDE_ROW_INTERP, XDE_ROW_COPY_A, XDE_ROW_COPY_B = 0, 1, 2
 XDE_NOISE_NORMAL, XDE_NOISE_BITS = 0, 1
+XDE_CDEHEAD_ACT_IDENTITY, XDE_CDEHEAD_ACT_TANH = 0, 1  # `act` of include/xde_hip_cdehead.h
+XDE_CDEHEAD_MAX_K = 256
+XDE_CDEHEAD_MAX_HC = 2147483392
 XDE_DDE_MAX_LAGS = 16  # delays of one xde_dde_tape_gather launch (include/xde_hip_dde.h)
 
 
@@ -1491,6 +1509,55 @@ class HipBackend:
         plan = XdeCdePlan()
         rc = self.lib.xde_cde_plan(int(bool(backward)), big.data_ptr(), int(B), int(H), int(channels), dtype_code(big.dtype), C.byref(plan))
         self._check(rc, "xde_cde_plan")
+        return _plan_dict(plan)
+
+    # -- the fused last layer of a CDE field (include/xde_hip_cdehead.h) --------------------------------------------------------------
+    # Private for the reason the _cde_* methods are.  Only CdeHeadFn and CDEField (xde/base_cde.py) call these.
+    def _cde_head_launch(self, who, big, gout, a, W, bias, series, coef, knots, t, method, act):
+        """One launch of xde_cdehead_forward (``gout`` None) or xde_cdehead_backward: the control as ``_cde_launch`` takes it (``coef`` not None: the natural control's ``Y, M``),
+        ``a [B, K]``, ``W [H C, K]``, ``bias [H C]`` or None, ``big`` = ``out [B, H]`` (``gout`` None) or ``s [B, H C]`` (``gout [B, H]``),
+        all contiguous on one device in one dtype; ``act`` "tanh" or None."""
+        operands = [x for x in (big, gout, a, W, bias, series, coef, knots) if x is not None]
+        self._spline_operands(who, *operands)
+        if act not in (None, "tanh"):
+            raise XdeError("{}: act must be 'tanh' or None, got {!r}".format(who, act))
+        if series.dim() != 3 or a.dim() != 2 or W.dim() != 2 or big.dim() != 2:
+            raise XdeError("{}: expected series [B, Tn, C], a [B, K], W [H C, K] and {}".format(who, "out [B, H]" if gout is None else "s [B, H C]"))
+        B, Tn, C_ = series.shape
+        K = a.shape[1]
+        H = W.shape[0] // C_
+        agree = (tuple(a.shape) == (B, K) and tuple(W.shape) == (H * C_, K) and H >= 1 and tuple(knots.shape) == (Tn,)
+                 and (bias is None or tuple(bias.shape) == (H * C_,)) and (coef is None or coef.shape == series.shape)
+                 and tuple(big.shape) == ((B, H) if gout is None else (B, H * C_)) and (gout is None or tuple(gout.shape) == (B, H)))
+        if not agree:
+            raise XdeError("{}: shapes do not agree: series {}, knots {}, a {}, W {}, bias {}, {} {}".format(
+                who, tuple(series.shape), tuple(knots.shape), tuple(a.shape), tuple(W.shape), None if bias is None else tuple(bias.shape),
+                "out" if gout is None else "s", tuple(big.shape)))
+        t_dev, t_host, tt = self._launch_time(who, t, series)
+        sym = "xde_cdehead_forward" if gout is None else "xde_cdehead_backward"
+        head = (big.data_ptr(),) if gout is None else (big.data_ptr(), gout.data_ptr())
+        rc = getattr(self.lib, sym)(*head, a.data_ptr(), W.data_ptr(), _ptr(bias), series.data_ptr(), _ptr(coef), knots.data_ptr(), t_dev,
+                                    t_host, tt, B, H, C_, K, Tn, HISTORY_METHODS[method] if coef is None else 0,
+                                    XDE_CDEHEAD_ACT_TANH if act == "tanh" else XDE_CDEHEAD_ACT_IDENTITY, dtype_code(series.dtype),
+                                    self._stream(series))
+        self._check(rc, sym)
+
+    def _cde_head(self, out, a, W, bias, series, coef, knots, t, method, act):
+        """``out[b, h] = sum_c act(a[b] . W[h C + c] + bias[h C + c]) * dX[b, c]`` with ``dX`` as in ``_cde_contract`` (``coef`` not None:
+        as in ``_cde_contract_natural``), in the order of include/xde_hip_cdehead.h.  One launch; ``[B, H, C]`` is never written."""
+        self._cde_head_launch("_cde_head", out, None, a, W, bias, series, coef, knots, t, method, act)
+
+    def _cde_head_backward(self, s, gout, a, W, bias, series, coef, knots, t, method, act):
+        """``s[b, h C + c] = gout[b, h] * dX[b, c] * act'(pre[b, h C + c])``: the cotangent of ``_cde_head``'s pre-activations.  One launch."""
+        self._cde_head_launch("_cde_head_backward", s, gout, a, W, bias, series, coef, knots, t, method, act)
+
+    def _cde_head_plan(self, B, H, channels, K, dtype, act):
+        """The launch plan of ``_cde_head`` / ``_cde_head_backward`` as a dict of xde_cdehead_plan_t's fields; ``served`` is 0 for
+        float64, ``K`` beyond the cap or an unknown ``act``.  Nothing is enqueued and no device is needed."""
+        plan = XdeCdeHeadPlan()
+        code = {None: XDE_CDEHEAD_ACT_IDENTITY, "tanh": XDE_CDEHEAD_ACT_TANH}.get(act, -1)
+        rc = self.lib.xde_cdehead_plan(int(B), int(H), int(channels), int(K), dtype_code(dtype), code, C.byref(plan))
+        self._check(rc, "xde_cdehead_plan")
         return _plan_dict(plan)
 
     # -- the natural cubic spline control (include/xde_hip_spline.h) -------------------------------------------------------------------

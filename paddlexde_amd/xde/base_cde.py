@@ -16,6 +16,10 @@ jumps at every knot: fixed-step solvers with the knots on their grid integrate i
 refused: its sliding four-row window is not a path through the data.  ``CubicHermiteSpline`` and ``LinearInterpolation`` keep the
 reference's scale conventions as written; these are exact on a uniform knot grid — the default ``t=None`` — only: for irregularly
 sampled data use ``NaturalCubicSpline``.
+
+The last layer.  A field that ends in ``Linear(K, H C)`` (+ ``tanh``) — every neural CDE's does — can say so with ``CDELinearHead``:
+``CDEField`` then computes that layer, the activation and the contraction in one launch (xde_cdehead_forward,
+include/xde_hip_cdehead.h) and ``F [B, H, C]`` is never written; see ``CDELinearHead`` for what is served and what takes the plain route.
 """
 import torch
 
@@ -23,7 +27,7 @@ from .. import _hip
 from ..interpolation import BezierSpline, CubicHermiteSpline, InterpolationBase, LinearInterpolation, NaturalCubicSpline
 from .base_ode import BaseODE
 
-__all__ = ["BaseCDE", "CDEField", "CdeContractFn", "CdeControlContractFn"]
+__all__ = ["BaseCDE", "CDEField", "CDELinearHead", "CdeContractFn", "CdeControlContractFn", "CdeHeadFn"]
 
 
 # The natural control has entry points of its own (its rows are ``Y`` and ``M``); every other control names its method.  Each kind of
@@ -111,6 +115,75 @@ class CdeControlContractFn(torch.autograd.Function):
         return gF, g_series, None, None, None, g_coef
 
 
+class CdeHeadFn(torch.autograd.Function):
+    """``out[b, h] = sum_c act(a[b] . W[h C + c] + bias[h C + c]) * X'(t)[b, c]`` for contiguous ``a [B, K]``, ``W [H C, K]``, ``bias
+    [H C]`` or None and the control's tensors as ``CdeContractFn`` takes them: a field's last linear layer, its activation and the
+    contraction as one xde_cdehead_forward launch (include/xde_hip_cdehead.h).  Nothing of size ``B H C`` is saved: the backward is one
+    xde_cdehead_backward launch that computes the pre-activations again and writes their cotangent ``s [B, H C]`` — freed when the
+    backward returns — and then ``ga = s W``, ``gW = s^T a``, ``gbias = sum_b s`` by torch (plain large GEMMs: the BLAS's).  The
+    control, the knots and ``t`` get no gradient."""
+
+    @staticmethod
+    def forward(ctx, a, W, bias, series, knots, t, method, coef, act):
+        a, W = a.contiguous(), W.contiguous()
+        bias = None if bias is None else bias.contiguous()
+        H = W.shape[0] // series.shape[-1]
+        out = torch.empty((a.shape[0], H), dtype=a.dtype, device=a.device)  # (torch's allocator: capture-safe)
+        natural = method == "natural"
+        _hip.get_backend()._cde_head(out, a, W, bias, series, coef if natural else None, knots, t, None if natural else method, act)
+        ctx.method, ctx.act, ctx.t_host, ctx.has_bias = method, act, None if torch.is_tensor(t) else t, bias is not None
+        ctx.save_for_backward(a, W, series, knots, *([bias] if bias is not None else []), *([coef] if natural else []),
+                              *([t] if torch.is_tensor(t) else []))
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        a, W, series, knots, *rest = ctx.saved_tensors
+        bias = rest.pop(0) if ctx.has_bias else None
+        natural = ctx.method == "natural"
+        coef = rest.pop(0) if natural else None
+        t = rest.pop(0) if ctx.t_host is None else ctx.t_host
+        s = torch.empty((a.shape[0], W.shape[0]), dtype=a.dtype, device=a.device)  # (every element is written by the launch)
+        _hip.get_backend()._cde_head_backward(s, gout.contiguous(), a, W, bias, series, coef, knots, t, None if natural else ctx.method,
+                                              ctx.act)
+        ga = torch.matmul(s, W) if ctx.needs_input_grad[0] else None
+        gW = torch.matmul(s.t(), a) if ctx.needs_input_grad[1] else None
+        gbias = s.sum(0) if bias is not None and ctx.needs_input_grad[2] else None
+        return ga, gW, gbias, None, None, None, None, None, None
+
+
+class CDELinearHead(torch.nn.Module):
+    """A CDE field that ends the way every neural CDE's does: ``act(head(trunk(t, z)))`` reshaped to ``[..., state, channels]``, with
+    ``head = nn.Linear(hidden, state * channels)`` and ``trunk`` any module or callable ``(t, z) -> [..., hidden]``.
+
+    Called on its own it is that plain composition — a valid ``func`` anywhere.  Inside ``CDEField`` (``cdeint``, ``cdeint_adjoint``)
+    the last layer, the activation and the contraction with ``X'(t)`` run as ONE launch and ``[B, state, channels]`` is never written
+    (``CdeHeadFn``), when the kernel serves the shape (float32, ``hidden`` up to the cap ``_hip.XDE_CDEHEAD_MAX_K``) and the control is
+    not ``differentiable=True``; every other case takes the plain composition and the contraction launch, as any ``func`` does.
+    ``activation`` is "tanh" or None (the identity).  ``fuse = False`` on an instance keeps it on the plain route."""
+
+    fuse = True
+
+    def __init__(self, trunk, hidden, state, channels, activation="tanh", bias=True):
+        super().__init__()
+        if activation not in ("tanh", None):
+            raise ValueError("CDELinearHead: activation must be 'tanh' or None (the identity), got {!r}".format(activation))
+        if not callable(trunk):
+            raise TypeError("CDELinearHead: trunk must be a module or a callable (t, z) -> [..., hidden], got {}".format(type(trunk)))
+        hidden, state, channels = int(hidden), int(state), int(channels)
+        if hidden < 1 or state < 1 or channels < 1:
+            raise ValueError("CDELinearHead: hidden, state and channels must be >= 1, got {}, {}, {}".format(hidden, state, channels))
+        self.trunk = trunk
+        self.head = torch.nn.Linear(hidden, state * channels, bias=bias)
+        self.hidden, self.state, self.channels, self.activation = hidden, state, channels, activation
+
+    def forward(self, t, z):
+        pre = self.head(self.trunk(t, z))
+        y = torch.tanh(pre) if self.activation == "tanh" else pre
+        return y.reshape(z.shape + (self.channels,))
+
+
 def _kernel_time(t, series):
     """``t`` as the kernels take it: one float32 / float64 element on the series' device, else a Python number."""
     if not torch.is_tensor(t):
@@ -152,6 +225,7 @@ class CDEField(torch.nn.Module):
         d["_coef"] = X._coef.reshape(d["_series"].shape) if isinstance(X, NaturalCubicSpline) else None
         # a control built with differentiable=True goes through CdeControlContractFn; every other one through CdeContractFn, as before
         d["_contract"] = CdeControlContractFn if getattr(X, "differentiable", False) else CdeContractFn
+        d["_head_served"] = {}  # (B, dtype, the head's sizes) -> whether the fused launch serves it
 
     def control_tensors(self):
         """The tensors of a differentiable control that ask for a gradient, as the contraction takes them: the series (linear /
@@ -160,7 +234,44 @@ class CDEField(torch.nn.Module):
             return ()
         return tuple(x for x in (self._series, self._coef) if x is not None and x.requires_grad)
 
+    def _fused_head(self, z):
+        """Whether ``forward`` takes the one-launch route of a ``CDELinearHead`` for this ``z``: the module has not opted out, the
+        control is not differentiable (that cotangent needs ``F``) and the kernel's plan serves the shape.  No launch."""
+        func = self.func
+        if not isinstance(func, CDELinearHead) or not func.fuse or self._contract is not CdeContractFn:
+            return False
+        if z.dtype not in (torch.float32, torch.float64) or z.dim() < 1 or func.channels != self._series.shape[-1]:
+            return False
+        B = max(1, z.numel() // max(1, z.shape[-1]))
+        key = (B, z.dtype, func.state, func.hidden, func.activation)
+        served = self._head_served.get(key)  # (the plan query is host arithmetic, but one ctypes call per evaluation adds up)
+        if served is None:
+            served = bool(_hip.get_backend()._cde_head_plan(B, func.state, func.channels, func.hidden, z.dtype, func.activation)["served"])
+            self._head_served[key] = served
+        return served
+
+    def _forward_head(self, t, z):
+        func, series = self.func, self._series
+        H, K = func.state, func.hidden
+        a = func.trunk(t, z)
+        if not torch.is_tensor(a) or tuple(a.shape) != tuple(z.shape[:-1]) + (K,) or z.shape[-1] != H:
+            raise ValueError("CDELinearHead: trunk(t, z) must return [..., hidden] = {} for z of shape [..., state] = {}, got {} for z {}".format(
+                tuple(z.shape[:-1]) + (K,), tuple(z.shape[:-1]) + (H,), tuple(a.shape) if torch.is_tensor(a) else type(a), tuple(z.shape)))
+        if a.dtype != z.dtype or a.device != z.device:
+            raise ValueError("trunk(t, z) must return z's dtype on z's device ({}, {}), got {}, {}".format(z.dtype, z.device, a.dtype, a.device))
+        if a.dtype != series.dtype:
+            raise ValueError("the control's series is {} and the state is {}: build X from a series of the state's dtype".format(
+                series.dtype, a.dtype))
+        if tuple(z.shape[:-1]) != self._lead:
+            raise ValueError("z has leading dimensions {} and the control's series {}: they must be the same".format(
+                tuple(z.shape[:-1]), self._lead))
+        out = CdeHeadFn.apply(a.reshape(-1, K), func.head.weight, func.head.bias, series, self._knots, _kernel_time(t, series), self._method,
+                              self._coef, func.activation)
+        return out.reshape(z.shape)
+
     def forward(self, t, z):
+        if self._fused_head(z):
+            return self._forward_head(t, z)
         F = self.func(t, z)
         series = self._series
         C = series.shape[-1]
