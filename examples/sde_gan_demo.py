@@ -24,6 +24,12 @@ two launches per step that stream ``g`` twice.  The default is Ito Euler-Maruyam
 ``--solver grheun`` is the paper's own scheme, reversible Heun on the ``[D, M]`` diffusion (``solver=GeneralReversibleHeun``:
 Stratonovich, one evaluation per step), and ``--adjoint`` trains the generator through ``sdeint_adjoint``, whose backward recomputes
 the path instead of keeping it: memory that does not grow with the number of steps.
+
+    python examples/sde_gan_demo.py --iters 200 --fused-head
+
+``--fused-head`` declares the generator's diffusion as an ``SDELinearHead``: under Euler its last layer, the ``tanh``, the product with
+the Brownian increment and the update are one launch per step, and the ``[B, D, M]`` matrix is neither written nor kept for the
+backward.  Heun and reversible Heun evaluate the same module as the plain composition.
 """
 import argparse
 import json
@@ -39,6 +45,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from paddlexde_amd.functional import cdeint, sdeint, sdeint_adjoint  # noqa: E402
 from paddlexde_amd.interpolation import CubicHermiteSpline  # noqa: E402
 from paddlexde_amd.solver import RK4, Euler, GeneralReversibleHeun, Heun  # noqa: E402
+from paddlexde_amd.xde import SDELinearHead  # noqa: E402
 
 
 def make_data(device, batch=64, T=17, t1=2.0, theta=1.0, mu=0.0, sigma=0.5, seed=0):
@@ -57,12 +64,17 @@ def make_data(device, batch=64, T=17, t1=2.0, theta=1.0, mu=0.0, sigma=0.5, seed
 class Generator(nn.Module):
     """latent [B, V] -> series [B, T]: hidden state D, Brownian motion M, diffusion ``[B, 1, D, M]``."""
 
-    def __init__(self, latent=4, hidden=16, noise=3, width=32, solver=Euler, adjoint=False):
+    def __init__(self, latent=4, hidden=16, noise=3, width=32, solver=Euler, adjoint=False, fused_head=False):
         super().__init__()
         self.latent, self.hidden, self.noise, self.solver, self.adjoint = latent, hidden, noise, solver, adjoint
         self.init = nn.Linear(latent, hidden)
         self.f_net = nn.Sequential(nn.Linear(hidden, width), nn.Softplus(), nn.Linear(width, hidden), nn.Tanh())
         self.g_net = nn.Sequential(nn.Linear(hidden, width), nn.Softplus(), nn.Linear(width, hidden * noise), nn.Tanh())
+        # the same network with its last layer declared (and shared: g_net[2] IS the head's linear layer), for the one-launch step
+        self.g_head = None
+        if fused_head:
+            self.g_head = SDELinearHead(lambda t, x: self.g_net[1](self.g_net[0](x)), width, hidden, noise)
+            self.g_head.head = self.g_net[2]
         self.readout = nn.Linear(hidden, 1)
 
     def f(self, t, x):
@@ -78,11 +90,12 @@ class Generator(nn.Module):
             options["step_size"] = step_size
         if seed is not None:
             options["seed"] = seed
+        g = self.g if self.g_head is None else self.g_head
         if self.adjoint and torch.is_grad_enabled():
             params = tuple(self.f_net.parameters()) + tuple(self.g_net.parameters())
             xs = sdeint_adjoint(self.f, self.g, x0, t, solver=self.solver, options=options, adjoint_params=params)
         else:
-            xs = sdeint(self.f, self.g, x0, t, solver=self.solver, options=options)  # [B, T, D]
+            xs = sdeint(self.f, g, x0, t, solver=self.solver, options=options)  # [B, T, D]
         return self.readout(xs).squeeze(-1)  # [B, T]
 
 
@@ -114,13 +127,13 @@ class Discriminator(nn.Module):
                 p.clamp_(-bound, bound)
 
 
-def train(iters=200, log_every=20, seed=0, device="cuda:0", batch=64, step_size=0.0625, solver=Euler, adjoint=False):
+def train(iters=200, log_every=20, seed=0, device="cuda:0", batch=64, step_size=0.0625, solver=Euler, adjoint=False, fused_head=False):
     """Alternate one discriminator and one generator step for ``iters`` iterations; returns one ``{"iters", "d_loss", "g_loss",
     "diffusion_grad"}`` per iteration, ``diffusion_grad`` the largest magnitude of the gradient the generator step left on the first
     weight of the generator's diffusion network."""
     torch.manual_seed(seed)
     t, real = make_data(device, batch=batch, seed=seed)
-    gen, dis = Generator(solver=solver, adjoint=adjoint).to(device), Discriminator().to(device)
+    gen, dis = Generator(solver=solver, adjoint=adjoint, fused_head=fused_head).to(device), Discriminator().to(device)
     g_opt = torch.optim.Adam(gen.parameters(), lr=2e-3, betas=(0.5, 0.9))
     d_opt = torch.optim.Adam(dis.parameters(), lr=4e-3, betas=(0.5, 0.9))
     latents = torch.Generator().manual_seed(seed + 1)
@@ -156,6 +169,8 @@ if __name__ == "__main__":
     ap.add_argument("--solver", choices=("euler", "heun", "grheun"), default="euler",
                     help="the generator's scheme: Ito Euler-Maruyama, Stratonovich Heun, or Stratonovich reversible Heun")
     ap.add_argument("--adjoint", action="store_true", help="with --solver grheun: train through sdeint_adjoint (constant memory)")
+    ap.add_argument("--fused-head", action="store_true", help="the generator's diffusion as an SDELinearHead: one launch per Euler step")
     a = ap.parse_args()
-    hist = train(a.iters, step_size=a.step_size, solver={"euler": Euler, "heun": Heun, "grheun": GeneralReversibleHeun}[a.solver], adjoint=a.adjoint)
+    hist = train(a.iters, step_size=a.step_size, solver={"euler": Euler, "heun": Heun, "grheun": GeneralReversibleHeun}[a.solver], adjoint=a.adjoint,
+                 fused_head=a.fused_head)
     print(json.dumps(hist[-1]))

@@ -288,6 +288,24 @@ HEADERS["xde_hip_teval.h"] = {
     "xde_teval_dense": (_i32, [_vp, _vp, _vp, _vpp, _dp, _i32, _vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _i32, _i32, _i64, _i64, _i64, _i32, _vp]),
     "xde_teval_cotangent": (_i32, [_vpp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _i32, _i32, C.c_uint32, _i64, _i64, _i64, _i32, _vp]),
 }
+
+
+class XdeSdeHeadPlan(C.Structure):
+    """Mirror of xde_sdehead_plan_t (include/xde_hip_sdehead.h)."""
+
+    _fields_ = [(name, C.c_int32) for name in ("served", "tiles", "tile_r", "tile_n", "pass_n", "kh", "kq", "kq_regs", "S", "Dc", "lds_w",
+                                               "lds_bytes", "k_cap")] + [("items", C.c_int64), ("blocks", C.c_int64)]
+
+
+# a matrix diffusion's last linear layer, its activation and the Euler-Maruyama step as one launch, and the cotangent of its
+# pre-activations (it stands before the table of xde_hip_gn.h, whose increments it shares: the order from there on is pinned by tests)
+HEADERS["xde_hip_sdehead.h"] = {
+    "xde_sdehead_step": (_i32, [_vp] * 6 + [_i64, _i32, _i32, _i32, _i32, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
+    "xde_sdehead_backward": (_i32, [_vp] * 6 + [_i64, _i32, _i32, _i32, _i32, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
+    "xde_sdehead_plan": (_i32, [_i64, _i32, _i32, _i32, _i32, _i32, C.POINTER(XdeSdeHeadPlan)]),
+}
+
+
 # the Euler-Maruyama step with general or scalar noise and its cotangents; the Heun step's two launches on such noise and theirs
 HEADERS["xde_hip_gn.h"] = {
     "xde_sde_gn_step": (_i32, [_vp] * 4 + [_i64, _i64, _i64, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
@@ -342,6 +360,9 @@ XDE_NOISE_NORMAL, XDE_NOISE_BITS = 0, 1
 XDE_CDEHEAD_ACT_IDENTITY, XDE_CDEHEAD_ACT_TANH = 0, 1  # `act` of include/xde_hip_cdehead.h
 XDE_CDEHEAD_MAX_K = 256
 XDE_CDEHEAD_MAX_HC = 2147483392
+XDE_SDEHEAD_ACT_IDENTITY, XDE_SDEHEAD_ACT_TANH = 0, 1  # `act` of include/xde_hip_sdehead.h
+XDE_SDEHEAD_MAX_K, XDE_SDEHEAD_PAIR_K = 256, 128
+XDE_SDEHEAD_MAX_DM = 2147483392
 XDE_DDE_MAX_LAGS = 16  # delays of one xde_dde_tape_gather launch (include/xde_hip_dde.h)
 
 
@@ -477,6 +498,19 @@ def logsig_channels(channels, depth):
 def _plan_dict(plan):
     """A launch plan (the mirror of one of the headers' ``xde_*_plan_t``) as a dict of its fields."""
     return {name: int(getattr(plan, name)) for name, _ in plan._fields_}
+
+
+def sde_head_plan(rows, D, M, K, dtype, act):
+    """The launch plan of the fused diffusion head (include/xde_hip_sdehead.h) as a dict of xde_sdehead_plan_t's fields; ``served`` is 0
+    for float64, ``K`` beyond the cap or an unknown ``act`` ("tanh" or None are known).  Host arithmetic of the library: nothing is
+    enqueued and no device or backend is needed, so the solvers can ask it before they choose a route."""
+    lib = load_library()
+    plan = XdeSdeHeadPlan()
+    code = {None: XDE_SDEHEAD_ACT_IDENTITY, "tanh": XDE_SDEHEAD_ACT_TANH}.get(act, -1)
+    rc = lib.xde_sdehead_plan(int(rows), int(D), int(M), int(K), dtype_code(dtype), code, C.byref(plan))
+    if rc != XDE_OK:
+        raise XdeError("xde_sdehead_plan failed (status {}): {}".format(rc, lib.xde_last_error().decode()))
+    return _plan_dict(plan)
 
 
 def _dbl_array(xs):
@@ -1139,6 +1173,55 @@ class HipBackend:
         if rows == 0:
             return
         self._check(self.lib.xde_sde_gn_backward(_ptr(gf), _ptr(gg), _ptr(gy1), rows, D, int(M), *tail), "xde_sde_gn_backward")
+
+    # -- the fused last layer of a matrix diffusion (include/xde_hip_sdehead.h) ----------------------------------------------------------
+    # Private for the reason _sde_em_step is.  Only FixedSolver._em_step under an SDELinearHead (and SdeHeadEulerFn) call these.
+    def _sde_head_call(self, who, state, big, a, W, bias, act):
+        """The operand check the two fused-head launches share; nothing is launched here.  ``state`` are contiguous device tensors of one
+        shape ``[.., D]`` and dtype (None: a null pointer), ``a`` is ``[.., K]`` with the same leading shape, ``W [D M, K]``, ``bias
+        [D M]`` or None, ``big`` None or ``[.., D M]``.  Returns ``(rows, D, M, K, act code)``."""
+        like = next(x for x in state if x is not None)
+        self._require_device(*state, big, a, W, bias)
+        if like.dim() < 1:
+            raise XdeError("{}: the state needs a last axis".format(who))
+        _require_alike(who, "state operands", like, state)
+        if act not in (None, "tanh"):
+            raise XdeError("{}: act must be 'tanh' or None, got {!r}".format(who, act))
+        D = like.shape[-1]
+        rows = like.numel() // D if D else 0
+        ok = all(x is None or (x.is_contiguous() and x.dtype == like.dtype and x.device == like.device) for x in (big, a, W, bias))
+        ok = ok and a.dim() >= 1 and W.dim() == 2 and a.shape[:-1] == like.shape[:-1] and a.shape[-1] == W.shape[1] and D >= 1
+        ok = ok and W.shape[0] >= D and W.shape[0] % D == 0 and (bias is None or tuple(bias.shape) == (W.shape[0],))
+        ok = ok and (big is None or tuple(big.shape) == tuple(like.shape[:-1]) + (W.shape[0],))
+        if not ok:
+            raise XdeError("{}: expected contiguous tensors of the state's dtype with shapes that agree: state {}, a {}, W {}, bias {}{}".format(
+                who, tuple(like.shape), tuple(a.shape), tuple(W.shape), None if bias is None else tuple(bias.shape),
+                "" if big is None else ", s {}".format(tuple(big.shape))))
+        return rows, D, W.shape[0] // D, W.shape[1], XDE_SDEHEAD_ACT_TANH if act == "tanh" else XDE_SDEHEAD_ACT_IDENTITY
+
+    def _sde_head_step(self, y1, y0, f, a, W, bias, act, dt, s, seed, k):
+        """``y1[.., d] = (y0 + f*dt)[.., d] + sum_m act(a . W[d M + m] + bias[d M + m]) * (s*Z[.., m])``, the sum sequential in m, Z as
+        in ``_sde_gn_step``, in the order of include/xde_hip_sdehead.h; ``y1`` may be ``y0``.  One launch; ``[.., D, M]`` is never written."""
+        rows, D, M, K, code = self._sde_head_call("_sde_head_step", (y1, y0, f), None, a, W, bias, act)
+        if rows == 0:
+            return
+        rc = self.lib.xde_sdehead_step(_ptr(y1), _ptr(y0), _ptr(f), _ptr(a), _ptr(W), _ptr(bias), rows, D, M, K, code, float(dt), float(s),
+                                       int(seed), int(k), dtype_code(y0.dtype), self._stream(y0))
+        self._check(rc, "xde_sdehead_step")
+
+    def _sde_head_backward(self, s_out, gf, gy1, a, W, bias, act, dt, s, seed, k):
+        """``s_out[.., d M + m] = (gy1[.., d] * (s*Z[.., m])) * act'(pre[.., d M + m])``, the cotangent of ``_sde_head_step``'s
+        pre-activations, and ``gf = gy1*dt`` (None: skipped).  One launch that computes the pre-activations again."""
+        rows, D, M, K, code = self._sde_head_call("_sde_head_backward", (gy1, gf), s_out, a, W, bias, act)
+        if rows == 0:
+            return
+        rc = self.lib.xde_sdehead_backward(_ptr(s_out), _ptr(gf), _ptr(gy1), _ptr(a), _ptr(W), _ptr(bias), rows, D, M, K, code, float(dt),
+                                           float(s), int(seed), int(k), dtype_code(gy1.dtype), self._stream(gy1))
+        self._check(rc, "xde_sdehead_backward")
+
+    def _sde_head_plan(self, rows, D, M, K, dtype, act):
+        """``sde_head_plan`` (below) as the backend method the launches' callers use."""
+        return sde_head_plan(rows, D, M, K, dtype, act)
 
     # -- the Heun step with general or scalar noise (include/xde_hip_gn.h) --------------------------------------------------------------
     # Private for the reason _sde_em_step is.  Only FixedSolver._heun_step under a non-diagonal BaseSDE (and its autograd nodes) call these.

@@ -62,7 +62,9 @@ def sdeint(
     ``y1 = (y0 + (f0 + f1)*(0.5*dt)) + (g0 @ w + g1 @ w)*0.5`` on the same ``w = sqrt(|dt|) * Z`` and the same sequential sums; its
     predictor launch keeps ``g0 @ w`` for the corrector, so a step streams the diffusion twice, not three times, and each launch's
     backward regenerates Z (xde_sde_gn_heun_predict / _correct / _backward).  Milstein, SRK, ReversibleHeun, ``sdeint_adjoint`` and
-    ``logqp`` take diagonal noise only and say so."""
+    ``logqp`` take diagonal noise only and say so.  A ``diffusion`` that is a ``paddlexde_amd.xde.SDELinearHead`` (float32, ``hidden``
+    up to 256) is stepped by ``solver=Euler`` in one launch that runs its last layer on the matrix cores and never writes
+    ``[.., D, M]``, forward or backward (include/xde_hip_sdehead.h); every other solver evaluates it as the plain module it is."""
     if isinstance(y0, (tuple, list)):
         raise NotImplementedError("sdeint takes a tensor y0, not a tuple: stack the members into one state tensor")
     if not (isinstance(solver, type) and issubclass(solver, FixedSolver)):

@@ -151,6 +151,45 @@ class SdeGnEulerFn(torch.autograd.Function):
         return (None,) * 5 + (gy if need_y else None, gf, gg)
 
 
+class SdeHeadEulerFn(torch.autograd.Function):
+    """SdeGnEulerFn's step on a diffusion that ends in a linear layer, ``g[.., d, m] = act(a . W[d M + m] + bias[d M + m])`` for
+    contiguous ``a [.., K]``, ``W [D M, K]`` and ``bias [D M]`` or None: the layer, its activation, the product with ``s*Z`` and the
+    update as one xde_sdehead_step launch (``HipBackend._sde_head_step``, include/xde_hip_sdehead.h).  The node saves ``a``, ``W``,
+    ``bias`` and the scalars — nothing of size ``rows D M``: backward is one xde_sdehead_backward launch that computes the
+    pre-activations again and writes their cotangent ``s [.., D M]`` (freed when the backward returns) and ``gf = gy1*dt``, then
+    ``ga = s W``, ``gW = s^T a``, ``gbias = sum s`` by torch (plain GEMMs: the BLAS's); ``gy0 = gy1`` needs no launch."""
+
+    @staticmethod
+    def forward(ctx, backend, dt, s, seed, k, act, y0, f, a, W, bias):
+        a, W = a.detach().contiguous(), W.detach().contiguous()
+        bias = None if bias is None else bias.detach().contiguous()
+        out = torch.empty_like(y0)
+        backend._sde_head_step(out, y0.detach(), f.detach(), a, W, bias, act, dt, s, seed, k)
+        ctx.backend, ctx.meta, ctx.act = backend, (float(dt), float(s), int(seed), int(k)), act
+        ctx.save_for_backward(a, W, *([bias] if bias is not None else []))
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        a, W, *rest = ctx.saved_tensors
+        bias = rest[0] if rest else None
+        need_y, need_f, need_a, need_W, need_b = ctx.needs_input_grad[6:11]
+        gy = _cotangent(gy)
+        gf = torch.empty_like(gy) if need_f else None
+        ga = gW = gbias = None
+        if need_a or need_W or (need_b and bias is not None):
+            s_out = torch.empty(tuple(gy.shape[:-1]) + (W.shape[0],), dtype=gy.dtype, device=gy.device)  # (every element is written)
+            ctx.backend._sde_head_backward(s_out, gf, gy, a, W, bias, ctx.act, *ctx.meta)
+            s2, a2 = s_out.reshape(-1, W.shape[0]), a.reshape(-1, W.shape[1])
+            ga = torch.matmul(s2, W).reshape(a.shape) if need_a else None
+            gW = torch.matmul(s2.t(), a2) if need_W else None
+            gbias = s2.sum(0) if need_b and bias is not None else None
+        elif gf is not None:
+            ctx.backend._sde_gn_backward(gf, None, gy, W.shape[0] // gy.shape[-1], *ctx.meta)  # (gf = gy1*dt: no matrix, no generator)
+        return (None,) * 6 + (gy if need_y else None, gf, ga, gW, gbias)
+
+
 class SdeGnHeunPredictFn(torch.autograd.Function):
     """Heun's predictor with general or scalar noise (``HipBackend._sde_gn_heun_predict``) as an autograd node with two outputs: ``yp``,
     SdeGnEulerFn's step, and ``a0 = g0 w``, the product the corrector takes instead of a second pass over ``g0``.  The node keeps only

@@ -19,10 +19,10 @@ import torch
 from .. import _hip
 from ..xde.base_dde import DDE_DAMPING, BaseDDE
 from ..xde.base_ode import BaseODE
-from ..xde.base_sde import BaseSDE
+from ..xde.base_sde import BaseSDE, SDELinearHead
 from ..xde.base_xde import BaseXDE
 from ._autograd import (CombineFn, InterpRowsFn, SdeEulerFn, SdeGnEulerFn, SdeKlAccFn, SdeKlEulerFn, SdeMilsteinFn, SdeRheunCorrectFn, SdeRheunPredictFn,
-                        SdeGnHeunCorrectFn, SdeGnHeunPredictFn, SdeGnRheunPredictFn, SdeSrkStage1Fn, SdeSrkStage2Fn, SdeSrkStepFn, SdeSupportFn)
+                        SdeGnHeunCorrectFn, SdeGnHeunPredictFn, SdeGnRheunPredictFn, SdeHeadEulerFn, SdeSrkStage1Fn, SdeSrkStage2Fn, SdeSrkStepFn, SdeSupportFn)
 from ._common import as_operand, np_dtype, storage_ptr, t_span_to_host, upload
 
 _one_third = 1 / 3
@@ -223,6 +223,7 @@ class FixedSolver(metaclass=abc.ABCMeta):
         self._tdev_cache = {}
         self._carry = None  # ReversibleHeun: the (yh, fh, gh) the last step left
         self._acc = None  # logqp: the running KL sum of every row the last step left (float64 y0.shape[:-1]; None: zero)
+        self._head_served = {}  # (rows, the head's sizes) -> whether the fused SDELinearHead launch serves it
 
     # -- per-step state ---------------------------------------------------------------------------
     def _arm(self, dt=None, t0_host=None, row=None, y1_out=None, k=None, ctrls=None, rec=None, dt_next=None):
@@ -293,7 +294,10 @@ class FixedSolver(metaclass=abc.ABCMeta):
         """One Ito Euler-Maruyama step of a BaseSDE: ``y1 = (y0 + f*dt) + g*(s*Z)``, ``s = sqrt(|dt|)`` in the state dtype, Z the
         normals of (xde.seed, grid step k) — one xde_sde_em_step launch (SdeEulerFn when an operand is differentiated).  Under general
         or scalar noise ``g`` is ``[.., D, M]`` and the step is ``y1 = (y0 + f*dt) + sum_m g[.., m]*(s*Z[.., m])``, Z over the flat
-        ``[rows, M]`` array: one xde_sde_gn_step launch in its place (SdeGnEulerFn).  Returns ``(y1, f)``."""
+        ``[rows, M]`` array: one xde_sde_gn_step launch in its place (SdeGnEulerFn) — or, where the diffusion is an ``SDELinearHead``
+        the kernel serves, ``_head_em_step``, which never forms ``g``.  Returns ``(y1, f)``."""
+        if self._matrix_noise and self._fused_head(y0):
+            return self._head_em_step(t0, y0, dt)
         f, g, dt, s, _, _, k, grad = self._sde_prologue(t0, dtt, y0, dt)
         if self._matrix_noise:
             if grad:
@@ -307,6 +311,47 @@ class FixedSolver(metaclass=abc.ABCMeta):
             return SdeEulerFn.apply(self.backend, dt, s, self.xde.seed, k, y0, f, g), f
         out = self._y1_out if self._y1_out is not None else torch.empty_like(y0)
         self.backend._sde_em_step(out, y0, f, g, dt, s, self.xde.seed, k)
+        return out, f
+
+    def _fused_head(self, y0):
+        """Whether ``_em_step`` takes the one-launch route of an ``SDELinearHead`` for this ``y0``: the diffusion is one and has not
+        opted out, its noise dimension is the problem's, the state is float32 and the kernel's plan serves the shape.  No launch."""
+        head = self.xde.g
+        if not isinstance(head, SDELinearHead) or not head.fuse or y0.dtype != torch.float32 or y0.dim() < 1:
+            return False
+        if self.xde.noise_dim not in (None, head.noise):  # (scalar noise with noise != 1: the plain route refuses it)
+            return False
+        rows = max(1, y0.numel() // max(1, y0.shape[-1]))
+        key = (rows, head.state, head.noise, head.hidden, head.activation)
+        served = self._head_served.get(key)  # (the plan query is host arithmetic, but one ctypes call per step adds up)
+        if served is None:
+            served = self._head_served[key] = bool(_hip.sde_head_plan(*key[:4], y0.dtype, head.activation)["served"])
+        return served
+
+    def _head_em_step(self, t0, y0, dt):
+        """``_em_step`` under general or scalar noise whose diffusion is an ``SDELinearHead``: ``f = drift(t0, y0)``,
+        ``a = trunk(t0, y0)`` and ONE xde_sdehead_step launch that runs the head's linear layer on the matrix cores, applies the
+        activation, meets ``s*Z`` and writes ``y1`` — ``g [.., D, M]`` is never written (SdeHeadEulerFn when an operand is
+        differentiated: nothing of that size is kept either).  ``nfe`` counts the step as ``_sde_prologue`` does."""
+        head, xde = self.xde.g, self.xde
+        self.nfe += 1
+        f = as_operand(xde.f(t0, y0), like=y0)
+        a = head.trunk(t0, y0)
+        want = tuple(y0.shape[:-1]) + (head.hidden,)
+        if not torch.is_tensor(a) or tuple(a.shape) != want or a.dtype != y0.dtype or a.device != y0.device or y0.shape[-1] != head.state:
+            got = "{} {}".format(tuple(a.shape), a.dtype) if torch.is_tensor(a) else type(a).__name__
+            raise ValueError("SDELinearHead: trunk(t, y) must return [..., hidden] = {} of dtype {} for y of shape [..., state] = {}, got {} "
+                             "for y {}".format(want, y0.dtype, tuple(y0.shape[:-1]) + (head.state,), got, tuple(y0.shape)))
+        xde.__dict__["noise_dim"] = head.noise
+        a = as_operand(a)
+        W, bias = head.head.weight, head.head.bias
+        dt, s = sde_step_scalars(dt, y0.dtype)
+        k = self._k if self._k is not None else 0
+        if torch.is_grad_enabled() and any(x is not None and x.requires_grad for x in (y0, f, a, W, bias)):
+            return SdeHeadEulerFn.apply(self.backend, dt, s, xde.seed, k, head.activation, y0, f, a, W, bias), f
+        out = self._y1_out if self._y1_out is not None else torch.empty_like(y0)
+        self.backend._sde_head_step(out, y0, f, a, as_operand(W.detach()), None if bias is None else as_operand(bias.detach()),
+                                    head.activation, dt, s, xde.seed, k)
         return out, f
 
     def _kl_em_step(self, t0, y0, f, g, dt, s, k, grad):

@@ -9,7 +9,8 @@ object: the noise of element e at grid step k is a function of (seed, k, e) — 
 
 ``noise_type="general"``: ``g(t, y)`` returns ``y.shape + (M,)`` and every row of the state (its last axis) is driven by an
 M-dimensional Brownian motion through its ``[D, M]`` matrix; ``"scalar"`` is ``M == 1``.  Euler maps such a problem onto
-xde_sde_gn_step (include/xde_hip_gn.h), whose normals are those of the flat ``[rows, M]`` array.
+xde_sde_gn_step (include/xde_hip_gn.h), whose normals are those of the flat ``[rows, M]`` array.  A diffusion declared as an
+``SDELinearHead`` (below) is stepped by Euler without ever forming that matrix: xde_sdehead_step (include/xde_hip_sdehead.h).
 """
 import numpy as np
 import torch
@@ -41,6 +42,39 @@ def check_noise_type(noise_type):
     if noise_type not in NOISE_TYPES:
         raise ValueError("noise_type must be 'diagonal', 'general' or 'scalar', got {!r}".format(noise_type))
     return noise_type
+
+
+class SDELinearHead(torch.nn.Module):
+    """A matrix diffusion that ends the way every SDE-GAN's and latent SDE's does: ``act(head(trunk(t, y)))`` reshaped to
+    ``[..., state, noise]``, with ``head = nn.Linear(hidden, state * noise)`` and ``trunk`` any module or callable
+    ``(t, y) -> [..., hidden]``.
+
+    Called on its own it is that plain composition — a valid ``g`` anywhere.  Under ``sdeint(..., solver=Euler)`` with ``noise_type``
+    "general" (or "scalar" with ``noise == 1``) the last layer, the activation, the product with the Brownian increment and the
+    Euler-Maruyama update run as ONE launch and ``[..., state, noise]`` is never written or kept for the backward
+    (``SdeHeadEulerFn``, include/xde_hip_sdehead.h), when the kernel serves the shape (float32, ``hidden`` up to the cap
+    ``_hip.XDE_SDEHEAD_MAX_K``); every other solver, dtype and shape takes the plain composition and the launches it always took.
+    ``activation`` is "tanh" or None (the identity).  ``fuse = False`` on an instance keeps it on the plain route."""
+
+    fuse = True
+
+    def __init__(self, trunk, hidden, state, noise, activation="tanh", bias=True):
+        super().__init__()
+        if activation not in ("tanh", None):
+            raise ValueError("SDELinearHead: activation must be 'tanh' or None (the identity), got {!r}".format(activation))
+        if not callable(trunk):
+            raise TypeError("SDELinearHead: trunk must be a module or a callable (t, y) -> [..., hidden], got {}".format(type(trunk)))
+        hidden, state, noise = int(hidden), int(state), int(noise)
+        if hidden < 1 or state < 1 or noise < 1:
+            raise ValueError("SDELinearHead: hidden, state and noise must be >= 1, got {}, {}, {}".format(hidden, state, noise))
+        self.trunk = trunk
+        self.head = torch.nn.Linear(hidden, state * noise, bias=bias)
+        self.hidden, self.state, self.noise, self.activation = hidden, state, noise, activation
+
+    def forward(self, t, y):
+        pre = self.head(self.trunk(t, y))
+        g = torch.tanh(pre) if self.activation == "tanh" else pre
+        return g.reshape(y.shape + (self.noise,))
 
 
 class BaseSDE(BaseXDE):
