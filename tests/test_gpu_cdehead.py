@@ -1,8 +1,13 @@
 """The fused last layer of a CDE field (include/xde_hip_cdehead.h) against float64 on the CPU: an error bound, determinism and row
 independence per shape — this kernel's sums run on the matrix cores, whose in-instruction order no host program can restate — and
-one solve through the public interface against the unfused route."""
+one solve through the public interface against the unfused route.  On small integer operands the sums over k are exact under any
+rounding, and there the launches are held to the header's float32 statement (tests/_head_exact.py, dX from the numpy doubles of the
+contraction and of the natural spline) bit for bit: the order of the runs of c, the carries, the element mapping.
+tests/_head_plans.py names the branches the shapes reach together; a sliced launch beyond the grid needs a small grid in a fresh
+process (tests/_head_grid_child.py)."""
 import copy
 import os
+import subprocess
 import sys
 
 import numpy as np
@@ -15,6 +20,11 @@ from paddlexde_amd.interpolation import CubicHermiteSpline, LinearInterpolation,
 from paddlexde_amd.solver import RK4
 from paddlexde_amd.xde import CDELinearHead
 
+from . import _head_exact as E
+from . import _head_plans as P
+from ._spline_double import SplineDoubleBackend
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 U = 2.0 ** -24
@@ -38,7 +48,14 @@ TABLE = [
     (70001, 1, 3, 1, 2, "cubic", True, "tanh", True),      # more work items than workgroups
     (33, 33, 1, 12, 8, "natural", True, None, True),
     (1, 7, 5, 33, 8, "linear", True, "tanh", False),
+    (33, 4, 5, 20, 8, "natural", True, "tanh", True),      # kq 3 of 4 registers; H C = 20 but the slices start at 5, 10, 15: s by element
+    (31, 2, 3, 24, 8, "cubic", True, "tanh", False),       # the instantiation of 4 again, H C % 4 != 0
+    (33, 2, 200, 72, 3, "linear", True, "tanh", False),    # kq 9 of 16: the k-loop leaves a group early; dX evaluated per use
+    (65, 3, 5, 128, 8, "cubic", False, "tanh", True),      # kq 16 of 16
+    (33, 3, 5, 136, 2, "linear", True, None, True),        # kq 17 of 32
+    (32 * 4096 + 33, 2, 3, 5, 2, "cubic", True, "tanh", True),  # 4098 work items on 2048 workgroups: second and third items
 ]
+MISALIGNED = (33, 7, 4, 8, 8, "natural", True, "tanh", True)  # K % 4 == 0 and H C % 4 == 0: only the pointers decide
 
 
 def gamma(n):
@@ -81,13 +98,111 @@ def reference(a, W, b, dX, gout, act):
     return out, out_bound, s.reshape(B, H * C), s_bound.reshape(B, H * C)
 
 
-def launch(be, a, W, b, series, coef, knots, t, method, act, gout):
+def off16(x):
+    """``x``'s elements in a contiguous tensor that starts one element past a 16-byte boundary."""
+    view = torch.empty(x.numel() + 4, dtype=x.dtype, device=x.device)[1:1 + x.numel()].view(x.shape)
+    view.copy_(x)
+    assert view.is_contiguous() and view.data_ptr() % 16 == 4
+    return view
+
+
+def launch(be, a, W, b, series, coef, knots, t, method, act, gout, misalign=False):
+    """Both directions.  ``misalign``: a, W and s one element off 16 bytes."""
     B, H = a.shape[0], W.shape[0] // series.shape[-1]
     out = torch.empty(B, H, device=DEV)
     s = torch.empty(B, W.shape[0], device=DEV)
+    if misalign:
+        a, W, s = off16(a), off16(W), off16(s)
     be._cde_head(out, a, W, b, series, coef, knots, t, method, act)
     be._cde_head_backward(s, gout, a, W, b, series, coef, knots, t, method, act)
     return out, s
+
+
+def features(B, H, C, K, backward, misalign=False):
+    return P.cde_features(_hip.get_backend()._cde_head_plan(B, H, C, K, torch.float32, None), B, H, C, K, backward, misalign)
+
+
+def control(row):
+    """The operands of ``make`` for a table row, the launch's time and method, and dX[B, C] from the numpy double, whose bits the
+    contraction's device functions are held to (tests/test_gpu_cde.py, tests/test_gpu_spline.py)."""
+    B, H, C, K, Tn, kind, bias, act, t_dev = row
+    a, W, b, X, series, coef, knots, gout = make(*row[:7])
+    t = 0.5 * (Tn - 1) + 0.125
+    tk = torch.tensor(t, dtype=torch.float64, device=DEV) if t_dev else t
+    double, th = SplineDoubleBackend(), torch.tensor(t, dtype=torch.float64) if t_dev else t
+    if kind == "natural":
+        dX = double._natural_dx(series.cpu(), coef.cpu(), knots.cpu(), th)
+    else:
+        dX = double._cde_dx(series.cpu(), knots.cpu(), th, kind)
+    return (a, W, b, gout), (series, coef, knots, tk, None if kind == "natural" else kind), np.ascontiguousarray(dX), X
+
+
+def check_integer_operands(be, row, misalign=False):
+    """a, W and bias small integers, identity: the sums over k are exact whatever the matrix instruction does inside (the condition is
+    asserted, not measured), so out and s must be the float32 statement of the header bit for bit.  gout and the control stay random
+    reals."""
+    B, H, C, K = row[:4]
+    (_, _, _, gout), ctl, dX, _ = control(row)
+    a, W, b = E.integer_operands(B, H * C, K, row[6])
+    assert E.integer_condition(a, W, b) < 2.0 ** 24
+    dev = [None if x is None else torch.from_numpy(x).to(DEV) for x in (a, W, b)]
+    out, s = launch(be, *dev, *ctl, None, gout.to(DEV), misalign=misalign)
+    assert np.array_equal(out.cpu().numpy(), E.cde_forward(a, W, b, dX)), ("out", row, misalign)
+    assert np.array_equal(s.cpu().numpy(), E.cde_backward(dX, gout.numpy())), ("s", row, misalign)
+
+
+def check_bounds(be, row, misalign=False):
+    """Random operands against float64 within the bounds of test_the_launches_are_within_their_bounds_of_float64_and_deterministic; dX
+    from the control's own derivative on the device, which must be the double's bits."""
+    B, H, C, K, Tn, kind, bias, act, t_dev = row
+    (a, W, b, gout), ctl, dX_double, X = control(row)
+    dX = X.derivative(torch.tensor([0.5 * (Tn - 1) + 0.125], device=DEV)).reshape(B, C).cpu()
+    assert np.array_equal(dX.numpy(), dX_double), ("dX", row)
+    dev = [None if x is None else x.to(DEV) for x in (a, W, b)]
+    out, s = launch(be, *dev, *ctl, act, gout.to(DEV), misalign=misalign)
+    ref, ref_bound, sref, sref_bound = reference(a, W, b, dX, gout, act)
+    for name, got, want, bound in (("out", out, ref, ref_bound), ("s", s, sref, sref_bound)):
+        err = (got.cpu().double() - want).abs()
+        print("{} {}: worst err / bound = {:.3f}".format(row, name, float((err / bound.clamp_min(1e-300)).max())))
+        assert bool((err <= bound).all()), (name, row, misalign)
+    return out, s
+
+
+def test_the_suites_shapes_reach_every_reachable_branch():
+    """Over every launch of this module's table and its misaligned shape at the default settings, per direction: all six instantiations,
+    every place the k-loop can leave early, every load and store decision, both dX sources, the tile and run edges, the slices, and
+    second and third work items (tests/_head_plans.py).  A condition, not a measurement: after a retune that moves a shape off its
+    branch this names the branch."""
+    for backward in (False, True):
+        seen = set().union(*(features(*row[:4], backward) for row in TABLE)) | features(*MISALIGNED[:4], backward, misalign=True)
+        assert P.gaps(P.cde_required(backward), seen) == [], backward
+
+
+@pytest.mark.parametrize("row", TABLE, ids=lambda r: "-".join(str(x) for x in r))
+def test_integer_operands_give_the_header_s_float32_statement_bit_for_bit(row):
+    check_integer_operands(_hip.get_backend(), row)
+
+
+def test_operands_one_element_off_16_bytes_give_the_aligned_launch_s_bits():
+    """a, W and s contiguous views that start 4 bytes past a 16-byte boundary, with K % 4 == 0 and H C % 4 == 0: the launch decides
+    for element access from the pointers alone, and nothing else may change."""
+    be = _hip.get_backend()
+    assert {"a:scalar-by-pointer", "W:scalar-by-pointer", "s-scalar-by-pointer"} <= features(*MISALIGNED[:4], True, misalign=True)
+    assert {"a:vec", "W:vec", "s-vec"} <= features(*MISALIGNED[:4], True)
+    assert all(torch.equal(x, y) for x, y in zip(check_bounds(be, MISALIGNED, misalign=True), check_bounds(be, MISALIGNED)))
+    check_integer_operands(be, MISALIGNED, misalign=True)
+
+
+def test_a_sliced_launch_beyond_the_grid_in_a_child_process():
+    """The plans the default settings cannot reach (the slicing keeps the items within the grid): a grid of 2 workgroups, read once
+    per process, so in a fresh child (tests/_head_grid_child.py) — sliced shapes take second and third work items with dX in LDS and
+    per use; the child asserts that from the plans and holds every launch to the integer statement bit for bit and to the float64
+    bounds."""
+    env = dict(os.environ, XDE_GRID_BLOCKS="2")
+    r = subprocess.run([sys.executable, "-m", "tests._head_grid_child", "cde"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    assert "CHILD DONE" in r.stdout, r.stdout[-2000:]
+    assert [line for line in r.stdout.splitlines() if line.startswith("FAIL ")] == []
 
 
 @pytest.mark.parametrize("row", TABLE, ids=lambda r: "-".join(str(x) for x in r))
