@@ -7,7 +7,10 @@ reference's RK4.  Model: Linear(2,50) -> Tanh -> Linear(50,2) applied to y^3, we
 mini-batches of (y0, t[:pred_len], y[:pred_len]) windows, loss = mean |pred - true|, RMSprop(lr=1e-3) — by back-propagating
 through odeint(RK4) (as the reference does) or with --adjoint through odeint_adjoint.
 
-    python examples/ode_demo.py --max-steps 200 [--adjoint] [--solver dopri5]
+    python examples/ode_demo.py --max-steps 200 [--adjoint] [--solver dopri5] [--fused-field]
+
+--fused-field builds the same network as an ``MLPField``: every evaluation that records no tape (the forward solve of --adjoint) is one
+launch instead of torch's five; the weights, their initialisation and the grad-enabled evaluations are unchanged.
 """
 import argparse
 import os
@@ -21,19 +24,21 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from paddlexde_amd import RK4, Dopri5, odeint, odeint_adjoint  # noqa: E402
 from paddlexde_amd.utils import _rms_norm  # noqa: E402
+from paddlexde_amd.xde import MLPField  # noqa: E402
 
 
 class ODEFunc(nn.Module):
-    def __init__(self):
+    def __init__(self, fused=False):
         super().__init__()
-        self.net = nn.Sequential(nn.Linear(2, 50), nn.Tanh(), nn.Linear(50, 2))
-        for m in self.net:
+        self.fused = fused
+        self.net = MLPField(2, 50) if fused else nn.Sequential(nn.Linear(2, 50), nn.Tanh(), nn.Linear(50, 2))
+        for m in self.net.modules():
             if isinstance(m, nn.Linear):
                 nn.init.normal_(m.weight, mean=0.0, std=0.1)
                 nn.init.zeros_(m.bias)
 
     def forward(self, t, y):
-        return self.net(y**3)
+        return self.net(t, y**3) if self.fused else self.net(y**3)
 
 
 def make_data(device, data_len=1000):
@@ -52,11 +57,11 @@ def get_batch(t, true_y, batch_size, pred_len, gen):
     return y0, t[:pred_len], true_y[win]  # [B, 2], [T], [B, T, 2]
 
 
-def train(max_steps=200, batch_size=20, pred_len=10, adjoint=False, solver="rk4", seed=42, device="cuda:0", log_every=50):
+def train(max_steps=200, batch_size=20, pred_len=10, adjoint=False, solver="rk4", seed=42, device="cuda:0", log_every=50, fused_field=False):
     torch.manual_seed(seed)
     gen = torch.Generator().manual_seed(seed)
     t, true_y = make_data(device)
-    func = ODEFunc().to(device)
+    func = ODEFunc(fused_field).to(device)
     opt = torch.optim.RMSprop(func.parameters(), lr=1e-3)
     S = {"rk4": RK4, "dopri5": Dopri5}[solver]
     losses = []
@@ -87,6 +92,7 @@ if __name__ == "__main__":
     ap.add_argument("--pred-len", type=int, default=10)
     ap.add_argument("--adjoint", action="store_true")
     ap.add_argument("--solver", default="rk4", choices=["rk4", "dopri5"])
+    ap.add_argument("--fused-field", action="store_true", help="the network as an MLPField: one launch per tape-free evaluation")
     a = ap.parse_args()
-    ls = train(a.max_steps, a.batch_size, a.pred_len, a.adjoint, a.solver)
+    ls = train(a.max_steps, a.batch_size, a.pred_len, a.adjoint, a.solver, fused_field=a.fused_field)
     print("first-10 mean loss {:.4f} -> last-10 mean loss {:.4f}".format(sum(ls[:10]) / 10, sum(ls[-10:]) / 10))

@@ -306,6 +306,21 @@ HEADERS["xde_hip_sdehead.h"] = {
 }
 
 
+class XdeMlpPlan(C.Structure):
+    """Mirror of xde_mlp_plan_t (include/xde_hip_mlp.h)."""
+
+    _fields_ = [(name, C.c_int32) for name in ("served", "tiles", "tile_r", "tile_n", "pass_n", "max_width", "x_vec", "out_vec", "lds_bytes",
+                                               "width_cap")] + [("items", C.c_int64), ("blocks", C.c_int64)]
+
+
+_i32p = C.POINTER(C.c_int32)
+# a neural ODE's whole vector field, a small MLP, as one launch (the newest table; the order of the four after it is pinned by tests)
+HEADERS["xde_hip_mlp.h"] = {
+    "xde_mlp_field": (_i32, [_vp, _vp, _vp, _dbl, _vpp, _vpp, _i32p, _i32, _i64, _i32, _i32, _i32, _vp]),
+    "xde_mlp_plan": (_i32, [_i64, _i32p, _i32, _i32, _i32, _i32, C.POINTER(XdeMlpPlan)]),
+}
+
+
 # the Euler-Maruyama step with general or scalar noise and its cotangents; the Heun step's two launches on such noise and theirs
 HEADERS["xde_hip_gn.h"] = {
     "xde_sde_gn_step": (_i32, [_vp] * 4 + [_i64, _i64, _i64, _dbl, _dbl, C.c_uint64, _i64, _i32, _vp]),
@@ -364,6 +379,8 @@ XDE_SDEHEAD_ACT_IDENTITY, XDE_SDEHEAD_ACT_TANH = 0, 1  # `act` of include/xde_hi
 XDE_SDEHEAD_MAX_K, XDE_SDEHEAD_PAIR_K = 256, 128
 XDE_SDEHEAD_MAX_DM = 2147483392
 XDE_DDE_MAX_LAGS = 16  # delays of one xde_dde_tape_gather launch (include/xde_hip_dde.h)
+XDE_MLP_ACT_IDENTITY, XDE_MLP_ACT_TANH = 0, 1  # `act` of include/xde_hip_mlp.h
+XDE_MLP_MAX_LAYERS, XDE_MLP_MAX_WIDTH, XDE_MLP_PAIR_WIDTH = 4, 256, 128
 
 
 class RowsCtl:
@@ -510,6 +527,24 @@ def sde_head_plan(rows, D, M, K, dtype, act):
     rc = lib.xde_sdehead_plan(int(rows), int(D), int(M), int(K), dtype_code(dtype), code, C.byref(plan))
     if rc != XDE_OK:
         raise XdeError("xde_sdehead_plan failed (status {}): {}".format(rc, lib.xde_last_error().decode()))
+    return _plan_dict(plan)
+
+
+def _mlp_act_code(act):
+    return {None: XDE_MLP_ACT_IDENTITY, "tanh": XDE_MLP_ACT_TANH}.get(act, -1)
+
+
+def mlp_field_plan(rows, widths, dtype, act, time=False):
+    """The launch plan of the fused MLP field (include/xde_hip_mlp.h) as a dict of xde_mlp_plan_t's fields.  ``widths`` are the input,
+    hidden and output sizes (one more than there are layers); ``served`` is 0 for float64, more than ``XDE_MLP_MAX_LAYERS`` layers, a
+    width beyond ``XDE_MLP_MAX_WIDTH`` or an unknown ``act`` ("tanh" or None are known).  Host arithmetic of the library: nothing is
+    enqueued and no device or backend is needed, so ``MLPField`` can ask it before it chooses a route."""
+    lib = load_library()
+    plan = XdeMlpPlan()
+    w = (C.c_int32 * len(widths))(*[int(x) for x in widths])
+    rc = lib.xde_mlp_plan(int(rows), w, len(widths) - 1, dtype_code(dtype), _mlp_act_code(act), int(bool(time)), C.byref(plan))
+    if rc != XDE_OK:
+        raise XdeError("xde_mlp_plan failed (status {}): {}".format(rc, lib.xde_last_error().decode()))
     return _plan_dict(plan)
 
 
@@ -1222,6 +1257,43 @@ class HipBackend:
     def _sde_head_plan(self, rows, D, M, K, dtype, act):
         """``sde_head_plan`` (below) as the backend method the launches' callers use."""
         return sde_head_plan(rows, D, M, K, dtype, act)
+
+    # -- a neural ODE's vector field as one launch (include/xde_hip_mlp.h) ---------------------------------------------------------------
+    # Private because the CPU test double implements the public methods only.  Only MLPField (xde/mlp_field.py) calls these.
+    def _mlp_field(self, out, x, t_rows, t, weights, biases, act, time):
+        """``out = L_n(act(... act(L_1(x)) ...))`` with ``L_l(h) = h @ weights[l].T + biases[l]`` (a None bias: none), in the order of
+        include/xde_hip_mlp.h.  ``x`` is ``[.., widths[0]]`` and ``out`` ``[.., widths[n]]``, contiguous float32 device tensors with the
+        same leading shape; with ``time`` the first weight has one more column, which multiplies ``t_rows`` (``[rows]`` floats on the
+        device) or, where that is None, the number ``t``.  One launch on the current stream; no hidden activation is written."""
+        who = "_mlp_field"
+        self._require_device(out, x, t_rows, *weights, *biases)
+        n = len(weights)
+        tensors = [out, x, t_rows] + list(weights) + list(biases)
+        ok = n >= 1 and len(biases) == n and all(z is None or (z.is_contiguous() and z.dtype == x.dtype and z.device == x.device) for z in tensors)
+        ok = ok and x.dim() >= 1 and out.dim() == x.dim() and out.shape[:-1] == x.shape[:-1] and all(w.dim() == 2 for w in weights)
+        widths = [x.shape[-1]] + [w.shape[0] for w in weights] if ok else []
+        for l in range(n if ok else 0):
+            ok = ok and weights[l].shape[1] == widths[l] + (1 if time and l == 0 else 0)
+            ok = ok and (biases[l] is None or tuple(biases[l].shape) == (widths[l + 1],))
+        ok = ok and out.shape[-1] == widths[-1] and x.shape[-1] >= 1
+        rows = x.numel() // x.shape[-1] if ok else 0
+        ok = ok and (t_rows is None or t_rows.numel() == rows)
+        if not ok:
+            raise XdeError("{}: expected contiguous tensors of one dtype and device with shapes that agree: x {}, out {}, weights {}".format(
+                who, tuple(x.shape), tuple(out.shape), [tuple(w.shape) for w in weights]))
+        if act not in (None, "tanh"):
+            raise XdeError("{}: act must be 'tanh' or None, got {!r}".format(who, act))
+        if rows == 0:
+            return
+        W = (C.c_void_p * n)(*[w.data_ptr() for w in weights])
+        B = (C.c_void_p * n)(*[_ptr(b) for b in biases])
+        rc = self.lib.xde_mlp_field(_ptr(out), _ptr(x), _ptr(t_rows), float(t), W, B, (C.c_int32 * (n + 1))(*widths), n, rows,
+                                    _mlp_act_code(act), int(bool(time)), dtype_code(x.dtype), self._stream(x))
+        self._check(rc, "xde_mlp_field")
+
+    def _mlp_plan(self, rows, widths, dtype, act, time=False):
+        """``mlp_field_plan`` (above) as the backend method the launch's caller uses."""
+        return mlp_field_plan(rows, widths, dtype, act, time)
 
     # -- the Heun step with general or scalar noise (include/xde_hip_gn.h) --------------------------------------------------------------
     # Private for the reason _sde_em_step is.  Only FixedSolver._heun_step under a non-diagonal BaseSDE (and its autograd nodes) call these.
