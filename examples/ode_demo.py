@@ -10,7 +10,8 @@ through odeint(RK4) (as the reference does) or with --adjoint through odeint_adj
     python examples/ode_demo.py --max-steps 200 [--adjoint] [--solver dopri5] [--fused-field]
 
 --fused-field builds the same network as an ``MLPField``: every evaluation that records no tape (the forward solve of --adjoint) is one
-launch instead of torch's five; the weights, their initialisation and the grad-enabled evaluations are unchanged.
+launch instead of torch's five, and with --adjoint every stage of the backward solve takes ``MLPField.vjp`` (two launches) through
+``adjoint_options["vjp"]`` instead of a taped evaluation and torch autograd; the weights and their initialisation are unchanged.
 """
 import argparse
 import os
@@ -40,6 +41,11 @@ class ODEFunc(nn.Module):
     def forward(self, t, y):
         return self.net(t, y**3) if self.fused else self.net(y**3)
 
+    def vjp(self, t, y, cotangent):
+        """adjoint_options["vjp"] of the fused field: MLPField.vjp at y**3 (two launches), and the cube's own factor on the state's part."""
+        f, vjp_t, vjp_u, *vjp_params = self.net.vjp(t, y**3, cotangent)
+        return (f, vjp_t, vjp_u * (3.0 * y * y), *vjp_params)
+
 
 def make_data(device, data_len=1000):
     A = torch.tensor([[-0.1, 2.0], [-2.0, -0.1]], device=device)
@@ -64,6 +70,7 @@ def train(max_steps=200, batch_size=20, pred_len=10, adjoint=False, solver="rk4"
     func = ODEFunc(fused_field).to(device)
     opt = torch.optim.RMSprop(func.parameters(), lr=1e-3)
     S = {"rk4": RK4, "dopri5": Dopri5}[solver]
+    hook = {"adjoint_options": {"vjp": func.vjp}} if fused_field and adjoint else {}  # the backward solve's stages in two launches each
     losses = []
     t0 = time.perf_counter()
     for step in range(1, max_steps + 1):
@@ -71,9 +78,9 @@ def train(max_steps=200, batch_size=20, pred_len=10, adjoint=False, solver="rk4"
         if S is RK4:
             # fixed solvers concatenate time on axis -2: give the state a length-1 time axis -> [B, T, 2]
             args = (func, y0[:, None, :], bt)
-            pred = (odeint_adjoint if adjoint else odeint)(*args, solver=RK4)
+            pred = (odeint_adjoint if adjoint else odeint)(*args, solver=RK4, **hook)
         else:
-            pred = odeint_adjoint(func, y0, bt, solver=Dopri5, rtol=1e-5, atol=1e-7, options={"norm": _rms_norm})  # [T, B, 2]
+            pred = odeint_adjoint(func, y0, bt, solver=Dopri5, rtol=1e-5, atol=1e-7, options={"norm": _rms_norm}, **hook)  # [T, B, 2]
             pred = pred.permute(1, 0, 2)
         loss = torch.mean(torch.abs(pred - by))
         opt.zero_grad()

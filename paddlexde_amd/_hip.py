@@ -313,11 +313,22 @@ class XdeMlpPlan(C.Structure):
                                                "width_cap")] + [("items", C.c_int64), ("blocks", C.c_int64)]
 
 
+class XdeMlpVjpPlan(C.Structure):
+    """Mirror of xde_mlp_vjp_plan_t (include/xde_hip_mlp.h)."""
+
+    _fields_ = [(name, C.c_int32) for name in ("served", "tile_r", "pitch", "sum_widths", "lds_bytes", "lds_cap", "grid_cap", "gx_vec")] + [
+        (name, C.c_int64) for name in ("params", "workspace_bytes", "items", "blocks")]
+
+
 _i32p = C.POINTER(C.c_int32)
-# a neural ODE's whole vector field, a small MLP, as one launch (the newest table; the order of the four after it is pinned by tests)
+# a neural ODE's whole vector field, a small MLP, as one launch, and its vector-Jacobian product as two (the newest table; the order of
+# the four after it is pinned by tests)
 HEADERS["xde_hip_mlp.h"] = {
     "xde_mlp_field": (_i32, [_vp, _vp, _vp, _dbl, _vpp, _vpp, _i32p, _i32, _i64, _i32, _i32, _i32, _vp]),
     "xde_mlp_plan": (_i32, [_i64, _i32p, _i32, _i32, _i32, _i32, C.POINTER(XdeMlpPlan)]),
+    "xde_mlp_field_vjp": (_i32, [_vp, _vp, _vpp, _vpp, _vp, _vp, _vp, _vp, _dbl, _vpp, _vpp, _i32p, _i32, _i64, _i32, _i32, _i32, _vp, _i64,
+                                 _i32, _vp]),
+    "xde_mlp_vjp_plan": (_i32, [_i64, _i32p, _i32, _i32, _i32, _i32, _i32, C.POINTER(XdeMlpVjpPlan)]),
 }
 
 
@@ -381,6 +392,7 @@ XDE_SDEHEAD_MAX_DM = 2147483392
 XDE_DDE_MAX_LAGS = 16  # delays of one xde_dde_tape_gather launch (include/xde_hip_dde.h)
 XDE_MLP_ACT_IDENTITY, XDE_MLP_ACT_TANH = 0, 1  # `act` of include/xde_hip_mlp.h
 XDE_MLP_MAX_LAYERS, XDE_MLP_MAX_WIDTH, XDE_MLP_PAIR_WIDTH = 4, 256, 128
+XDE_MLP_VJP_LDS_BYTES, XDE_MLP_VJP_MAX_BLOCKS = 65536, 256
 
 
 class RowsCtl:
@@ -545,6 +557,20 @@ def mlp_field_plan(rows, widths, dtype, act, time=False):
     rc = lib.xde_mlp_plan(int(rows), w, len(widths) - 1, dtype_code(dtype), _mlp_act_code(act), int(bool(time)), C.byref(plan))
     if rc != XDE_OK:
         raise XdeError("xde_mlp_plan failed (status {}): {}".format(rc, lib.xde_last_error().decode()))
+    return _plan_dict(plan)
+
+
+def mlp_vjp_plan(rows, widths, dtype, act, time=False, max_blocks=0):
+    """The plan of the fused MLP field's vector-Jacobian product (include/xde_hip_mlp.h) as a dict of xde_mlp_vjp_plan_t's fields;
+    ``served`` is 0 where ``mlp_field_plan``'s is and where the widths sum beyond the LDS bound.  ``max_blocks`` > 0 limits the
+    workgroups, and with them ``workspace_bytes``.  Host arithmetic of the library, as ``mlp_field_plan``."""
+    lib = load_library()
+    plan = XdeMlpVjpPlan()
+    w = (C.c_int32 * len(widths))(*[int(x) for x in widths])
+    rc = lib.xde_mlp_vjp_plan(int(rows), w, len(widths) - 1, dtype_code(dtype), _mlp_act_code(act), int(bool(time)), int(max_blocks),
+                              C.byref(plan))
+    if rc != XDE_OK:
+        raise XdeError("xde_mlp_vjp_plan failed (status {}): {}".format(rc, lib.xde_last_error().decode()))
     return _plan_dict(plan)
 
 
@@ -1294,6 +1320,45 @@ class HipBackend:
     def _mlp_plan(self, rows, widths, dtype, act, time=False):
         """``mlp_field_plan`` (above) as the backend method the launch's caller uses."""
         return mlp_field_plan(rows, widths, dtype, act, time)
+
+    def _mlp_field_vjp(self, f, gx, gW, gb, gt, x, a, t_rows, t, weights, biases, act, time, workspace, max_blocks=0):
+        """``f`` as ``_mlp_field``'s ``out`` (its bits) and the cotangent ``a`` (``f``'s shape) carried back through every layer, in the
+        order of include/xde_hip_mlp.h: ``gx`` (``x``'s shape), ``gW[l]`` (``weights[l]``'s shape), ``gb[l]`` (``[widths[l + 1]]``, or
+        None: not wanted) and, with ``time``, the 0-d ``gt``.  ``workspace`` is a float32 device tensor of at least the plan's
+        ``workspace_bytes`` that the call overwrites.  Two launches on the current stream; nothing hidden is written."""
+        who = "_mlp_field_vjp"
+        n = len(weights)
+        tensors = [f, gx, gt, x, a, t_rows, workspace] + list(weights) + list(biases) + list(gW) + list(gb)
+        self._require_device(*tensors)
+        ok = n >= 1 and len(biases) == len(gW) == len(gb) == n and all(
+            z is None or (z.is_contiguous() and z.dtype == x.dtype and z.device == x.device) for z in tensors)
+        ok = ok and x.dim() >= 1 and x.shape[-1] >= 1 and f.shape[:-1] == x.shape[:-1] and all(w.dim() == 2 for w in weights)
+        ok = ok and gx.shape == x.shape and a.shape == f.shape and (gt is not None and gt.numel() == 1 if time else True)
+        widths = [x.shape[-1]] + [w.shape[0] for w in weights] if ok else []
+        for l in range(n if ok else 0):
+            ok = ok and weights[l].shape[1] == widths[l] + (1 if time and l == 0 else 0) and gW[l].shape == weights[l].shape
+            ok = ok and all(b is None or tuple(b.shape) == (widths[l + 1],) for b in (biases[l], gb[l]))
+        ok = ok and f.shape[-1] == widths[-1]
+        rows = x.numel() // x.shape[-1] if ok else 0
+        ok = ok and (t_rows is None or t_rows.numel() == rows)
+        if not ok:
+            raise XdeError("{}: expected contiguous tensors of one dtype and device with shapes that agree: x {}, a {}, f {}, gx {}, "
+                           "weights {}".format(who, tuple(x.shape), tuple(a.shape), tuple(f.shape), tuple(gx.shape),
+                                               [tuple(w.shape) for w in weights]))
+        if act not in (None, "tanh"):
+            raise XdeError("{}: act must be 'tanh' or None, got {!r}".format(who, act))
+        if rows == 0:
+            return
+        ptrs = lambda xs: (C.c_void_p * n)(*[_ptr(z) for z in xs])  # noqa: E731
+        rc = self.lib.xde_mlp_field_vjp(_ptr(f), _ptr(gx), ptrs(gW), ptrs(gb), _ptr(gt), _ptr(x), _ptr(a), _ptr(t_rows), float(t),
+                                        ptrs(weights), ptrs(biases), (C.c_int32 * (n + 1))(*widths), n, rows, _mlp_act_code(act),
+                                        int(bool(time)), dtype_code(x.dtype), _ptr(workspace), workspace.numel() * workspace.element_size(),
+                                        int(max_blocks), self._stream(x))
+        self._check(rc, "xde_mlp_field_vjp")
+
+    def _mlp_vjp_plan(self, rows, widths, dtype, act, time=False, max_blocks=0):
+        """``mlp_vjp_plan`` (above) as the backend method the launches' caller uses."""
+        return mlp_vjp_plan(rows, widths, dtype, act, time, max_blocks)
 
     # -- the Heun step with general or scalar noise (include/xde_hip_gn.h) --------------------------------------------------------------
     # Private for the reason _sde_em_step is.  Only FixedSolver._heun_step under a non-diagonal BaseSDE (and its autograd nodes) call these.
